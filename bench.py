@@ -3,13 +3,23 @@
 of the hybrid PVConv backbone at B=8, N=20000 points, xyz+rgb (README.md:153,
 BASELINE.json configs[1]) -- on N MI355X GPUs, data parallel.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0.  value = points/s of the whole job
-(world * B * N * K / max-over-ranks wall time of K steps); inputs are resident
-in HBM before the timed region.  Besides the contract fields it carries:
+(world * B * N * K / max-over-ranks wall time of K steps), ms_per_step = that
+wall time / K in ms; inputs are resident in HBM before the timed region.
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the line;
+the fields below that need runs of their own are null or empty in it
+(roofline_step is arithmetic on ms_per_step and stays).  --dump-outputs DIR
+also writes what the last timed step returned and updated (dump_outputs) as
+DIR/<name>.npy; model init, batch and the steps' draws are seeded, so equal
+arguments give equal inputs.  --full adds every other leg (the untimed profiled
+steps and the HIP events around the roofline kernels inside the timed region,
+Chamfer / EMD / ball query, CPU baseline).  With --full, besides the contract
+fields, the line carries:
   roofline      the dominant hot-path kernel (by time inside the step), its
                 algorithmic FLOPs / its HIP-event time
   roofline_step the whole step: sum_k FLOP_k / peak_k / t_step, against
@@ -186,7 +196,18 @@ def parse():
     p.add_argument("--no-event-timing", action="store_true")
     p.add_argument("--profile-steps", type=int, default=2,
                    help="untimed steps with HIP events around every op (per-kernel table)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beside the headline figure: per-kernel table and "
+                        "rooflines, Chamfer / EMD / ball query, CPU baseline (each can be "
+                        "dropped again with its --no-... option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned and updated to DIR/<name>.npy")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.no_cpu_baseline = args.no_chamfer = args.no_event_timing = True
+    return args
 
 
 def chamfer_ms(dev, b, n, m, iters=20):
@@ -335,6 +356,36 @@ def ball_query_ms(dev, b, n, m, radius, u, iters=5):
             "distance_tests_per_s_upper": b * m * n / (ms * 1e-3)}
 
 
+DUMP_MAX_ELEMS = 2 << 20       # per array: 8 MiB of float32, 5 state arrays -> 40 MiB in all
+
+
+def dump_outputs(tr, last, out_dir):
+    """--dump-outputs: what a caller of the timed path holds after its last step,
+    as float32 DIR/<name>.npy -- the losses `Trainer.step` returned, the clipped
+    gradient norm, and the state the step updated (every tensor of the three
+    models' state dicts and of the two EMA shadows, flattened and concatenated in
+    state-dict order).  An array of more than DUMP_MAX_ELEMS elements is written as
+    a fixed sample: the elements at sorted(default_rng(0).integers(0, n, MAX))."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss_point": last["loss_point"].reshape(1),
+              "loss_latent": last["loss_latent"].reshape(1)}
+    if tr.last_grad_norm is not None:
+        arrays["grad_norm"] = torch.as_tensor(tr.last_grad_norm).reshape(1)
+    for name, state in (("state_enc", tr.enc.state_dict()), ("state_pf", tr.pf.state_dict()),
+                        ("state_lf", tr.lf.state_dict()), ("ema_pf", tr.ema_pf.shadow),
+                        ("ema_lf", tr.ema_lf.shadow)):
+        arrays[name] = torch.cat([v.detach().reshape(-1).float() for v in state.values()])
+    for name, t in arrays.items():
+        n = t.numel()
+        if n > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, n, DUMP_MAX_ELEMS))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.detach().to("cpu", torch.float32).numpy())
+        log(f"dumped {name}: {t.numel()} of {n} elements")
+
+
 def launch_ranks(args, backend):
     """`bench.py --gpus N` run directly (no WORLD_SIZE in the env): start N ranks
     as a `torch.distributed.run` child -- the reference's `torchrun --standalone
@@ -454,6 +505,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     loss_p, loss_z = float(last["loss_point"]), float(last["loss_latent"])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, last, args.dump_outputs)
 
     if rank == 0:
         points = world * cfg.batch_size * cfg.num_points * args.steps
@@ -569,7 +622,7 @@ def main():
             "B=8, N=20000", f"B={cfg.batch_size}, N={cfg.num_points}")
         line = {
             "metric": metric, "value": value, "unit": "points/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms, "full": args.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "vs_h100_derived_upper_bound": value / H100_DERIVED_PTS,
             "dtype": "fp32 ContextNet (scatter/gather ops fp32; Conv3d + 1x1 convs as bf16x3 "

@@ -25,7 +25,9 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-BENCHQ="--no-cpu-baseline --no-chamfer"
+# every bench task reads fields only a --full run fills (rooflines, per-kernel table)
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
+BENCHQ="--full --no-cpu-baseline --no-chamfer"
 for task in "$@"; do
   echo "[gpu.sh] $task $(date +%T)"
   case "$task" in
