@@ -361,7 +361,10 @@ int pcfm_conv3d_igemm_cl_list(const void* xs, const void* wsplit, const float* b
                               int which, float* y, void* ws, size_t ws_bytes, void* stream);
 /* pcfm_conv3d_wgrad_cl with x a voxelized grid: steps whose X rows are all
  * empty voxels are skipped (bit-identical to pcfm_conv3d_wgrad_cl); workspace
- * pcfm_conv3d_wgrad_occ_workspace_bytes (adds the per-split chunk lists). */
+ * pcfm_conv3d_wgrad_occ_workspace_bytes (adds the per-split chunk lists).
+ * Every shape pcfm_conv3d_wgrad_cl takes is taken: where a split lists more
+ * chunks than the K-slice masks have LDS room for (1792), only the chunk lists
+ * are used -- decided before anything is launched. */
 size_t pcfm_conv3d_wgrad_occ_workspace_bytes(int b, int cin, int cout, int r);
 int pcfm_conv3d_wgrad_cl_occ(const void* xs, const void* gys, int b, int cin, int cout, int r,
                              const unsigned* masks, float* grad_w, void* ws, size_t ws_bytes,

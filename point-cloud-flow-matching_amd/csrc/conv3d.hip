@@ -2405,6 +2405,11 @@ static int wgrad_cl(const void* xs, const void* gys, int b, int cin, int cout, i
     int* lists = nullptr;
     int* counts = nullptr;
     const int cap = wgrad_cap(b, r, S);
+    // decided before anything is launched: the K-slice masks of a split's chunks
+    // are staged in LDS behind the two buffers; where they do not fit the kernel
+    // runs without them (the skip only drops exact-zero products)
+    if (kmask != nullptr && 2 * (size_t)kW3Buf + (size_t)cap * 16 > (size_t)kLdsBytesMax)
+      kmask = nullptr;
     if (cmask != nullptr) {
       const size_t lb = (size_t)9 * S * cap * sizeof(int), cb = (size_t)9 * S * sizeof(int);
       PCFM_CHECK_ARG(ws_bytes >= need + lb + cb,
@@ -2415,8 +2420,6 @@ static int wgrad_cl(const void* xs, const void* gys, int b, int cin, int cout, i
                          b * (V / kWV), S, cap, lists, counts);
     }
     const size_t lds = 2 * (size_t)kW3Buf + (kmask != nullptr ? (size_t)cap * 16 : 0);
-    PCFM_CHECK_ARG(lds <= (size_t)kLdsBytesMax, "conv3d_wgrad_cl_occ: %d listed chunks per split "
-                   "exceed the LDS", cap);
     hipLaunchKernelGGL(conv3_wgrad3_kernel, dim3(tiles / 3 * S), dim3(kW3Threads), lds, st,
                        xh, xh + kSplitLo, gh, gh + kSplitLo, b, cin, cout, r,
                        S, (float*)ws, lists, counts, cap, kmask);

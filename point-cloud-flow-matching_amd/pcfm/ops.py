@@ -767,7 +767,8 @@ def conv3d_forward(x: torch.Tensor, weight: torch.Tensor, bias) -> torch.Tensor:
     cout = weight.shape[0]
     img = conv3d_prep_weight(weight, False)
     y = torch.empty((b, cout, r, r, r), dtype=torch.float32, device=x.device)
-    bias_p = _ptr(bias.contiguous()) if bias is not None else None
+    bias_c = bias.contiguous() if bias is not None else None  # alive across the call
+    bias_p = _ptr(bias_c) if bias_c is not None else None
     ws = _workspace(_lib.query("pcfm_conv3d_igemm_workspace_bytes", b, cin, cout, r), x)
     with _timed("conv3d_fwd", 54 * b * r ** 3 * cin * cout, x, "mfma"):
         _lib.call("pcfm_conv3d_igemm", _ptr(x), _ptr(img), bias_p, b, cin, cout, r, _ptr(y),
@@ -860,7 +861,8 @@ def conv3d_igemm_split(xs: torch.Tensor, img: torch.Tensor, bias, b: int, cin: i
     (pcfm_conv3d_igemm_cl_list: mode 1 -> the neighbourhood-occupied voxels,
     bias elsewhere; mode 2 -> the occupied voxels, 0 elsewhere)."""
     y = torch.empty((b, cout, r, r, r), dtype=torch.float32, device=xs.device)
-    bias_p = _ptr(bias.contiguous()) if bias is not None else None
+    bias_c = bias.contiguous() if bias is not None else None  # alive across the call
+    bias_p = _ptr(bias_c) if bias_c is not None else None
     ws = _workspace(_lib.query("pcfm_conv3d_igemm_cl_workspace_bytes", b, cin, cout, r), xs)
     if occ_mode and (occ is not None or vlists is not None):
         op = op + "_sparse"  # skips work: timed apart from the dense launches (roofline)
@@ -920,7 +922,8 @@ def pointwise_forward(x: torch.Tensor, weight: torch.Tensor, bias) -> torch.Tens
     cout = weight.shape[0]
     img = pointwise_prep_weight(weight, False)
     y = torch.empty((b, cout, n), dtype=torch.float32, device=x.device)
-    bias_p = _ptr(bias.contiguous()) if bias is not None else None
+    bias_c = bias.contiguous() if bias is not None else None  # alive across the call
+    bias_p = _ptr(bias_c) if bias_c is not None else None
     with _timed("pointwise_fwd", 2 * b * n * cin * cout, x, "mfma"):
         _lib.call("pcfm_pointwise_gemm", _ptr(x), _ptr(img), bias_p, b, cin, cout, n, _ptr(y),
                   _stream(x))
@@ -941,7 +944,8 @@ def pointwise_forward_bnstats(x: torch.Tensor, weight: torch.Tensor, bias):
     img = pointwise_prep_weight(weight, False)
     y = torch.empty((b, cout, n), dtype=torch.float32, device=x.device)
     stats = torch.empty((cout, groups, 2), dtype=torch.float32, device=x.device)
-    bias_p = _ptr(bias.contiguous()) if bias is not None else None
+    bias_c = bias.contiguous() if bias is not None else None  # alive across the call
+    bias_p = _ptr(bias_c) if bias_c is not None else None
     with _timed("pointwise_fwd", 2 * b * n * cin * cout, x, "mfma"):
         _lib.call("pcfm_pointwise_gemm_bnstats", _ptr(x), _ptr(img), bias_p, b, cin, cout, n,
                   _ptr(y), _ptr(stats), _stream(x))
@@ -1526,6 +1530,7 @@ def gn_film_res_backward_bnin(dout, y, bn_mean, bn_invstd, bn_weight, bn_bias, s
     dbeta (B, C), bnpart (C, P, 2)): dz = dL/dz and the BatchNorm backward
     statistics for bn_act_backward_parts."""
     dout = dout.contiguous()
+    gamma = gamma.contiguous()
     b, c, n = y.shape
     P = _lib.query("pcfm_gn_bnin_parts", b, n)
     if P <= 0:
@@ -1540,7 +1545,7 @@ def gn_film_res_backward_bnin(dout, y, bn_mean, bn_invstd, bn_weight, bn_bias, s
     with _timed("gn_film_res_bwd", 4 * 5 * y.numel(), y):
         _lib.call("pcfm_gn_film_res_bwd_bnin", _ptr(dout), _ptr(y), _ptr(bn_mean),
                   _ptr(bn_invstd), _ptr(bn_weight), _ptr(bn_bias), float(slope), _ptr(weight),
-                  _ptr(bias), _ptr(gamma.contiguous()), _ptr(mean), _ptr(rstd), b, c, n, groups,
+                  _ptr(bias), _ptr(gamma), _ptr(mean), _ptr(rstd), b, c, n, groups,
                   _ptr(dz), _ptr(dw), _ptr(dbias), _ptr(dgamma), _ptr(dbeta), _ptr(bnpart),
                   _ptr(ws), ws.numel(), _stream(y))
     return dz, dw, dbias, dgamma, dbeta, bnpart
@@ -1597,6 +1602,7 @@ def gn_silu_backward(dout, x, weight, bias, mean, rstd, groups: int):
 def gn_film_res_backward(dout, x, weight, bias, gamma, mean, rstd, groups: int):
     """-> (dx, dweight, dbias, dgamma (B, C), dbeta (B, C))"""
     dout = dout.contiguous()
+    gamma = gamma.contiguous()
     b, c, n = x.shape
     dx = torch.empty_like(x)
     small = torch.empty((2 * c + 2 * b * c,), dtype=torch.float32, device=x.device)
@@ -1606,7 +1612,7 @@ def gn_film_res_backward(dout, x, weight, bias, gamma, mean, rstd, groups: int):
     ws = _workspace(_lib.query("pcfm_gn_film_workspace_bytes", b, c, n, groups), x)
     with _timed("gn_film_res_bwd", 4 * 5 * x.numel(), x):
         _lib.call("pcfm_gn_film_res_bwd", _ptr(dout), _ptr(x), _ptr(weight), _ptr(bias),
-                  _ptr(gamma.contiguous()), _ptr(mean), _ptr(rstd), b, c, n, groups, _ptr(dx),
+                  _ptr(gamma), _ptr(mean), _ptr(rstd), b, c, n, groups, _ptr(dx),
                   _ptr(dw), _ptr(dbias), _ptr(dgamma), _ptr(dbeta), _ptr(ws), ws.numel(),
                   _stream(x))
     return dx, dw, dbias, dgamma, dbeta
