@@ -155,6 +155,19 @@ SIGNATURES = {
 
 ABI_VERSION = 20
 
+# name -> (restype, argtypes); every symbol of include/pcfm_chamfer_nd.h (the
+# D-component Chamfer entries: a sibling header with its own version, reached
+# through the same call() / query())
+ND_SIGNATURES = {
+    "pcfm_chamfer_nd_abi_version": (_I, []),
+    "pcfm_chamfer_nd_supported": (_I, [_I]),
+    "pcfm_chamfer_nd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "pcfm_chamfer_nd_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
+    "pcfm_chamfer_nd_bwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+}
+
+ND_ABI_VERSION = 1
+
 _lock = threading.Lock()
 _lib = None
 
@@ -176,13 +189,18 @@ def load() -> ctypes.CDLL:
                     "`python -c 'import __graft_entry__ as g; g.build()'` "
                     "(HIP tensors have no fallback)")
             lib = ctypes.CDLL(LIB_PATH)
-            for name, (res, args) in SIGNATURES.items():
-                fn = getattr(lib, name)
-                fn.restype = res
-                fn.argtypes = args
+            for table in (SIGNATURES, ND_SIGNATURES):
+                for name, (res, args) in table.items():
+                    fn = getattr(lib, name)
+                    fn.restype = res
+                    fn.argtypes = args
             v = lib.pcfm_abi_version()
             if v != ABI_VERSION:
                 raise RuntimeError(f"pcfm: ABI version {v} != expected {ABI_VERSION}; rebuild")
+            v = lib.pcfm_chamfer_nd_abi_version()
+            if v != ND_ABI_VERSION:
+                raise RuntimeError(f"pcfm: chamfer_nd ABI version {v} != expected "
+                                   f"{ND_ABI_VERSION}; rebuild")
             _lib = lib
     return _lib
 

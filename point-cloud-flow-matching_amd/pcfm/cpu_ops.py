@@ -31,7 +31,7 @@ __all__ = [
     "avg_voxelize_forward", "avg_voxelize_backward", "trilinear_devoxelize_forward",
     "trilinear_devoxelize_backward", "ball_query", "grouping_forward", "grouping_backward",
     "chamfer_forward", "chamfer_backward", "approxmatch_forward", "matchcost_forward",
-    "matchcost_backward",
+    "matchcost_backward", "chamfer_nd_forward", "chamfer_nd_backward",
 ]
 
 # rows of the query set per pairwise block (bounds the (rows, M) temporaries)
@@ -200,8 +200,23 @@ def grouping_backward(grad_y: torch.Tensor, indices: torch.Tensor, n: int):
 
 
 # ---------------------------------------------------------------------------
-# Chamfer-3D (chamfer3D.cu:12-195)
+# Chamfer (chamfer3D.cu:12-195; D components: chamfer{2,5,6}D, csrc/chamfer_nd.hip)
 # ---------------------------------------------------------------------------
+def _sqdist_nd(d):
+    """Squared length of d (..., D) along the last axis, D >= 2, as ONE float32
+    chain: acc = d1*d1; acc = fma(d0, d0, acc); acc = fma(dk, dk, acc) for
+    k = 2..D-1 (include/pcfm_chamfer_nd.h).  At D = 3 this is _sqdist."""
+    if d.dtype != torch.float32:
+        acc = d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]
+        for k in range(2, d.shape[-1]):
+            acc = acc + d[..., k] * d[..., k]
+        return acc
+    acc = _fma32(d[..., 0], d[..., 0], d[..., 1] * d[..., 1])
+    for k in range(2, d.shape[-1]):
+        acc = _fma32(d[..., k], d[..., k], acc)
+    return acc
+
+
 def _nn(q: torch.Tensor, p: torch.Tensor):
     """Nearest p for each q: (dist (b, nq), idx (b, nq) int32), lowest index on ties."""
     b, nq, _ = q.shape
@@ -216,8 +231,7 @@ def _nn(q: torch.Tensor, p: torch.Tensor):
         for j0 in range(0, nq, rows):
             qb = q[bb, j0:j0 + rows]
             # dx = candidate - query (chamfer3D.cu:32-35)
-            d = _sqdist(pb[None, :, 0] - qb[:, None, 0], pb[None, :, 1] - qb[:, None, 1],
-                        pb[None, :, 2] - qb[:, None, 2])
+            d = _sqdist_nd(pb[None, :, :] - qb[:, None, :])
             val, arg = torch.min(d, dim=1)  # first minimum on ties
             dist[bb, j0:j0 + qb.shape[0]] = val
             idx[bb, j0:j0 + qb.shape[0]] = arg.to(torch.int32)
@@ -243,10 +257,17 @@ def chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1,
         if q.shape[1] == 0 or p.shape[1] == 0:
             continue
         ixl = ix.long()
-        matched = torch.gather(p, 1, ixl[:, :, None].expand(-1, -1, 3))
+        gat = ixl[:, :, None].expand(-1, -1, q.shape[2])
+        matched = torch.gather(p, 1, gat)
         t = (gd * 2.0)[:, :, None] * (q - matched)
         gq.add_(t)
-        gp.scatter_add_(1, ixl[:, :, None].expand(-1, -1, 3), -t)
+        gp.scatter_add_(1, gat, -t)
+
+
+# the same two functions under the names of the D-component entry points: the
+# point dimension is read from the tensors
+chamfer_nd_forward = chamfer_forward
+chamfer_nd_backward = chamfer_backward
 
 
 # ---------------------------------------------------------------------------

@@ -619,6 +619,93 @@ chamfer_3D = types.SimpleNamespace(forward=_chamfer_forward, backward=_chamfer_b
 
 
 # --------------------------------------------------------------------------
+# chamfer_2D / chamfer_5D / chamfer_6D (ChamferDistancePytorch/chamfer{2,5,6}D/
+# chamfer_cuda.cpp): the same contract over D-component points
+# (include/pcfm_chamfer_nd.h, csrc/chamfer_nd.hip)
+# --------------------------------------------------------------------------
+def _chamfer_nd_shapes(xyz1, xyz2, d, per_point, per_coord):
+    """(b, n, m, d) after checking every extent the kernels index with."""
+    if xyz1.dim() != 3 or xyz2.dim() != 3:
+        raise RuntimeError("xyz1 / xyz2 must be (B, N, D) and (B, M, D)")
+    b, n, dim = xyz1.shape
+    m = xyz2.shape[1]
+    d = dim if d is None else d
+    if dim != d or tuple(xyz2.shape) != (b, m, d):
+        raise RuntimeError(f"expected (B, N, {d}) and (B, M, {d}), got {tuple(xyz1.shape)} and "
+                           f"{tuple(xyz2.shape)}")
+    for t, nm, k in per_point:      # k: 0 -> n rows, 1 -> m rows
+        if tuple(t.shape) != (b, (n, m)[k]):
+            raise RuntimeError(f"{nm} has shape {tuple(t.shape)}, expected {(b, (n, m)[k])}")
+    for t, nm, k in per_coord:
+        if tuple(t.shape) != (b, (n, m)[k], d):
+            raise RuntimeError(f"{nm} has shape {tuple(t.shape)}, expected {(b, (n, m)[k], d)}")
+    if d not in (2, 3, 5, 6):
+        raise RuntimeError(f"unsupported point dimension {d}")
+    return b, n, m, d
+
+
+def _chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2, d=None) -> int:
+    """Point dimension d (None: the tensors' last dimension) in {2, 3, 5, 6}."""
+    try:
+        host = _host(xyz1, xyz2, dist1, dist2, idx1, idx2)
+        for t, nm, k in ((xyz1, "xyz1", "f"), (xyz2, "xyz2", "f"), (dist1, "dist1", "f"),
+                         (dist2, "dist2", "f"), (idx1, "idx1", "i"), (idx2, "idx2", "i")):
+            (_check_host if host else _check)(t, nm, k)
+        b, n, m, d = _chamfer_nd_shapes(xyz1, xyz2, d, ((dist1, "dist1", 0), (dist2, "dist2", 1),
+                                                        (idx1, "idx1", 0), (idx2, "idx2", 1)), ())
+        if host:
+            cpu_ops.chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2)
+            return 1
+        ws = _workspace(_lib.query("pcfm_chamfer_nd_workspace_bytes", b, n, m, d), xyz1)
+        _lib.call("pcfm_chamfer_nd_fwd", _ptr(xyz1), _ptr(xyz2), b, n, m, d, _ptr(dist1),
+                  _ptr(dist2), _ptr(idx1), _ptr(idx2), _ptr(ws), ws.numel(), _stream(xyz1))
+    except RuntimeError as e:
+        print(f"error in nnd updateOutput: {e}")
+        return 0
+    return 1
+
+
+def _chamfer_nd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2,
+                         d=None) -> int:
+    try:
+        host = _host(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2)
+        for t, nm, k in ((xyz1, "xyz1", "f"), (xyz2, "xyz2", "f"), (gradxyz1, "gradxyz1", "f"),
+                         (gradxyz2, "gradxyz2", "f"), (graddist1, "graddist1", "f"),
+                         (graddist2, "graddist2", "f"), (idx1, "idx1", "i"), (idx2, "idx2", "i")):
+            (_check_host if host else _check)(t, nm, k)
+        b, n, m, d = _chamfer_nd_shapes(
+            xyz1, xyz2, d, ((graddist1, "graddist1", 0), (graddist2, "graddist2", 1),
+                            (idx1, "idx1", 0), (idx2, "idx2", 1)),
+            ((gradxyz1, "gradxyz1", 0), (gradxyz2, "gradxyz2", 1)))
+        if host:
+            cpu_ops.chamfer_nd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2,
+                                        idx1, idx2)
+            return 1
+        _lib.call("pcfm_chamfer_nd_bwd", _ptr(xyz1), _ptr(xyz2), b, n, m, d, _ptr(graddist1),
+                  _ptr(graddist2), _ptr(idx1), _ptr(idx2), _ptr(gradxyz1), _ptr(gradxyz2),
+                  _stream(xyz1))
+    except RuntimeError as e:
+        print(f"error in nnd get grad: {e}")
+        return 0
+    return 1
+
+
+def _chamfer_nd_namespace(d):
+    def forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
+        return _chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2, d)
+
+    def backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
+        return _chamfer_nd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1,
+                                    idx2, d)
+    return types.SimpleNamespace(forward=forward, backward=backward)
+
+
+chamfer_2D = _chamfer_nd_namespace(2)
+chamfer_5D = _chamfer_nd_namespace(5)
+chamfer_6D = _chamfer_nd_namespace(6)
+
+
+# --------------------------------------------------------------------------
 # emd_cuda (PyTorchEMD/cuda/emd.cpp:8-27): float and double
 # --------------------------------------------------------------------------
 def _emd_check(xyz1, xyz2):

@@ -290,8 +290,15 @@ def generate(pf, lf, batch_size: int, num_points: int, point_dim: int, latent_di
 def chamfer_l2(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """Per-cloud mean squared NN distance both ways (train.py:80-84); (B,)."""
     if pred.is_cuda and pred.dtype == torch.float32 and target.dtype == torch.float32:
-        from chamfer3D.dist_chamfer_3D import chamfer_3DDist
-        d1, d2, _, _ = chamfer_3DDist()(pred.contiguous(), target.contiguous())
+        dim = pred.shape[-1] if pred.dim() == 3 and target.dim() == 3 else 3
+        if dim in (2, 5, 6) and target.shape[-1] == dim:
+            # coloured / planar clouds: the D-component kernel (csrc/chamfer_nd.hip)
+            import importlib
+            dist = getattr(importlib.import_module(f"chamfer{dim}D.dist_chamfer_{dim}D"),
+                           f"chamfer_{dim}DDist")
+        else:
+            from chamfer3D.dist_chamfer_3D import chamfer_3DDist as dist
+        d1, d2, _, _ = dist()(pred.contiguous(), target.contiguous())
         return d1.mean(dim=1) + d2.mean(dim=1)
     d2 = torch.cdist(pred, target, p=2).pow(2)
     return d2.min(dim=2).values.mean(dim=1) + d2.min(dim=1).values.mean(dim=1)
