@@ -19,6 +19,10 @@
 //                   unit, register run-accumulators per tap flushed into a
 //                   wave-private LDS tile, coalesced tile store
 //   5. seg_part_sum adds the partial tiles of tiles split over several units
+//   3'. seg_ldsrow1  replaces 3-5 for the one-tap scatters whose item row fits
+//                   LDS (n <= kLdsRowMaxItems): one block per (batch, channel)
+//                   holds the row in sorted order in LDS and sums every
+//                   voxel's segment from there -- no transposed copy in HBM
 //
 // Used by avg_voxelize forward (key = voxel, term = feat * (1/cnt)),
 // trilinear devoxelize backward (key = base cell inds[b,0,:], term = wgt * g
@@ -686,11 +690,217 @@ __global__ void __launch_bounds__(256)
   }
 }
 
+// --------------------------------------------------------------------------
+// 3' + 4': the LDS-row apply (TAPS == 1), for item rows that fit LDS.  One
+// (batch, channel) item row is 4 n bytes (80 KB at N = 20000), so instead of
+// transposing (B, C, N) into channels-last rows in HBM (seg_rows), reading
+// them back (seg_unit_gather) and adding partial tiles (seg_part_sum), ONE
+// block per (batch, channel):
+//   stage   streams in[b, c, 0..n) and rank[b, 0..n) coalesced and stores
+//           row[rank[i]] = in[i] (rank is a permutation: no atomics); after one
+//           barrier LDS holds the channel's items in sorted order;
+//   sum     lane per voxel, 64-voxel chunks dealt round-robin to the waves:
+//           out[b, c, v] = sum of row[start[v] .. start[v+1]) * (1 / count when
+//           averaging), term by term in sorted (= item) order;
+//   crowd   the SAME SUMS IN THE SAME ORDER as the unit gather + seg_part_sum,
+//           so both engines return the same bits: a kTV-voxel tile of T > kItems
+//           items is cut into P = ceil(T / kItems) pieces [T p / P, T (p+1) / P)
+//           of its sorted items (the work units); a voxel's items inside one
+//           piece are summed in order from 0, and the voxel's piece sums are
+//           added in piece order.  A voxel inside one piece is still one lane's
+//           in-order sum.  A voxel that straddles pieces (at most one per piece
+//           boundary: <= n / kItems of them, the centre cells of a Gaussian
+//           cloud -- 2,372 points in one r = 8 voxel) goes on an LDS list (int
+//           atomic: the list's ORDER is arrival order, but a listed voxel's sum
+//           does not depend on who takes it) and is summed by a group of 16
+//           lanes, a lane per piece, then folded in piece order.
+// Every out element is written exactly once (zeros for empty voxels); HBM sees
+// the input row once and the output row once.  The sum is bound by instruction
+// issue, not by LDS or HBM (measured: DESIGN.md section 4, scatter step 7), so
+// it spends instructions per 64-voxel chunk sparingly: start[v + 1] comes from
+// the next lane, empty chunks only store zeros, the tile arithmetic runs only
+// in a chunk of more than kItems items, 1 / count is computed instead of loaded.
+// grid = (C, B), 1024 threads: two blocks per CU while 4 n <= 80 KB.
+// --------------------------------------------------------------------------
+constexpr int kLdsRowMaxItems = 40000;  // item row + crowd list <= the dynamic-LDS cap
+constexpr int kRowThreads = 1024;
+constexpr int kRowChunks = 4;  // 64-voxel chunks per wave per round (their plan loads in flight)
+// item loads per thread in flight while staging: the whole row of N = 20000 in
+// ONE round of 1024 threads (a block's stage is a chain of load round trips)
+constexpr int kRowStage = 20;
+constexpr int kRowAhead = 8;  // LDS reads in flight per lane in the in-order sum
+constexpr int kRowPad = kRowAhead;  // floats past the row, so the read-ahead stays inside LDS
+constexpr int kRowGroup = 16;  // lanes (pieces at a time) per listed voxel
+static_assert(64 % kTV == 0 && (kTV & (kTV - 1)) == 0, "tiles must not cross 64-voxel chunks");
+
+inline size_t seg_ldsrow_lds(int n) {
+  return (size_t)(n + kRowPad) * sizeof(float) + (size_t)(n / kItems + 1) * sizeof(int);
+}
+static_assert((size_t)(kLdsRowMaxItems + kRowPad) * 4 + (size_t)(kLdsRowMaxItems / kItems + 1) * 4 <=
+                  (size_t)kLdsBytesMax - 1024,
+              "the LDS row of kLdsRowMaxItems items exceeds the dynamic-LDS cap");
+static_assert((long long)kLdsRowMaxItems * (kLdsRowMaxItems / kItems + 2) < (1LL << 31),
+              "piece arithmetic is done in int");
+
+// The average pool's per-term factor, the bits seg_sort writes to vinv as
+// (float)(1.0 / (double)c) (vox.cu:66).  The correctly rounded fp32 quotient is
+// that value: rounding 1/c to double first could only matter if 1/c lay within
+// 2^-53 (relative) of the midpoint M / 2^j of two floats (M odd, j <= 25 +
+// log2 c), but |1/c - M / 2^j| >= 1 / (c 2^j) unless c is a power of two
+// (1/c exact), and 2^j < 2^53 for every c < 2^28.
+__device__ __forceinline__ float seg_inv_count(int c) {
+  return c > 0 ? 1.0f / (float)c : 0.0f;
+}
+
+// The piece (work unit) of a tile's item j, 0 <= j < T: the p with
+// T p / P <= j < T (p + 1) / P (integer divisions, as the unit gather cuts).
+__device__ __forceinline__ int seg_piece(int j, int T, int P) {
+  return ((j + 1) * P - 1) / T;
+}
+
+// row[a .. e) * s summed in order from 0, kRowAhead LDS reads in flight; reads
+// past e stay inside the padded row.
+__device__ __forceinline__ float seg_row_sum(const float* row, int a, int e, float s) {
+  float acc = 0.0f;
+  int i = a;
+  for (; i + kRowAhead <= e; i += kRowAhead) {
+    float x[kRowAhead];
+#pragma unroll
+    for (int q = 0; q < kRowAhead; ++q) x[q] = row[i + q];
+#pragma unroll
+    for (int q = 0; q < kRowAhead; ++q) acc = acc + x[q] * s;
+  }
+  if (i < e) {
+    float x[kRowAhead - 1];
+#pragma unroll
+    for (int q = 0; q < kRowAhead - 1; ++q) x[q] = row[i + q];
+#pragma unroll
+    for (int q = 0; q < kRowAhead - 1; ++q)
+      if (i + q < e) acc = acc + x[q] * s;
+  }
+  return acc;
+}
+
+__global__ void __launch_bounds__(kRowThreads)
+    seg_ldsrow1_kernel(const float* __restrict__ in, const int* __restrict__ rank,
+                       const int* __restrict__ start, int avg, int C, int n, int V,
+                       float* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) float row[];  // [n + pad] items, the crowd list
+  __shared__ int nlist;
+  int* list = reinterpret_cast<int*>(row + n + kRowPad);
+  const int lcap = n / kItems + 1;
+  const int c = blockIdx.x, b = blockIdx.y;
+  const int t = threadIdx.x, lane = t & 63;
+  constexpr int nt = kRowThreads, nw = kRowThreads / 64;
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  if (t == 0) nlist = 0;
+  const float* __restrict__ ib = in + ((size_t)b * C + c) * n;
+  const int* __restrict__ rb = rank + (size_t)b * n;
+  for (int i0 = t; i0 < n; i0 += kRowStage * nt) {
+    float x[kRowStage];
+    int rk[kRowStage];  // loads first (independent, in flight together), then the LDS stores
+#pragma unroll
+    for (int q = 0; q < kRowStage; ++q) {
+      const int i = i0 + q * nt;
+      rk[q] = i < n ? rb[i] : -1;
+      x[q] = i < n ? nt_ld(ib + i) : 0.0f;
+    }
+#pragma unroll
+    for (int q = 0; q < kRowStage; ++q)
+      if ((unsigned)rk[q] < (unsigned)n) row[rk[q]] = x[q];
+  }
+  __syncthreads();
+
+  const int* __restrict__ sb = start + (size_t)b * (V + 1);
+  float* __restrict__ ob = out + ((size_t)b * C + c) * V;
+  const int nchunks = (V + 63) >> 6;
+  for (int c0 = w; c0 < nchunks; c0 += kRowChunks * nw) {
+    int s0[kRowChunks], s1[kRowChunks];
+#pragma unroll
+    for (int u = 0; u < kRowChunks; ++u) {  // lanes past V: the empty segment at start[V]
+      const int ch = min(c0 + u * nw, nchunks - 1);
+      s0[u] = sb[min(ch * 64 + lane, V)];
+      s1[u] = sb[min(ch * 64 + 64, V)];  // one address per wave: the chunk's end
+    }
+#pragma unroll
+    for (int u = 0; u < kRowChunks; ++u) {
+      if (c0 + u * nw >= nchunks) break;  // wave-uniform
+      const int v = (c0 + u * nw) * 64 + lane;
+      const int nx = __shfl_down(s0[u], 1, 64);  // start[v + 1] from the next lane
+      const int a = max(s0[u], 0), e = min(lane < 63 ? nx : s1[u], n);
+      if (!__any(e > a)) {  // an empty chunk (most of the r = 32 grid)
+        if (v < V) ob[v] = 0.0f;
+        continue;
+      }
+      if (s1[u] - __builtin_amdgcn_readfirstlane(s0[u]) > kItems) {  // wave-uniform
+        // the kTV-voxel tile's items (tiles are aligned inside the 64-aligned chunk)
+        const int tA = __shfl(a, lane & ~(kTV - 1), 64);
+        const int T = __shfl(e, lane | (kTV - 1), 64) - tA;
+        if (T > kItems && e > a) {
+          const int P = (T + kItems - 1) / kItems;
+          if (seg_piece(a - tA, T, P) != seg_piece(e - 1 - tA, T, P)) {
+            const int slot = atomicAdd(&nlist, 1);
+            if (slot < lcap) list[slot] = v;
+            continue;
+          }
+        }
+      }
+      const float acc = seg_row_sum(row, a, e, avg ? seg_inv_count(e - a) : 1.0f);
+      if (v < V) ob[v] = acc;
+    }
+  }
+  __syncthreads();
+  // the listed voxels: a group of kRowGroup lanes each, a lane per piece
+  const int nl = min(nlist, lcap);
+  const int sub = lane & (kRowGroup - 1), gbase = lane & ~(kRowGroup - 1);
+  constexpr int kGroups = kRowThreads / kRowGroup;
+  for (int e0 = 0; e0 < nl; e0 += kGroups) {
+    const int ei = e0 + t / kRowGroup;
+    int v = 0, a = 0, e = 0, tA = 0, T = 1, P = 1, pl = 0, ph = -1;
+    if (ei < nl) {
+      v = list[ei];
+      a = max(sb[v], 0);
+      e = min(sb[v + 1], n);
+      tA = max(sb[v & ~(kTV - 1)], 0);
+      T = max(min(sb[min((v | (kTV - 1)) + 1, V)], n) - tA, 1);
+      P = (T + kItems - 1) / kItems;
+      pl = seg_piece(a - tA, T, P);
+      ph = seg_piece(e - 1 - tA, T, P);
+    }
+    const float s = avg ? seg_inv_count(e - a) : 1.0f;
+    float total = 0.0f;
+    for (int k = 0; __any(pl + k <= ph); k += kRowGroup) {
+      const int p = pl + k + sub;
+      float part = 0.0f;
+      if (p <= ph) {
+        const int pb = tA + T * p / P, pe = tA + T * (p + 1) / P;
+        part = seg_row_sum(row, max(a, pb), min(e, pe), s);
+      }
+#pragma unroll
+      for (int j = 0; j < kRowGroup; ++j) {  // fold in piece order
+        const float pj = __shfl(part, gbase + j, 64);
+        if (pl + k + j <= ph) total = (k + j == 0) ? pj : total + pj;
+      }
+    }
+    if (sub == 0 && ei < nl) ob[v] = total;
+  }
+}
+
 }  // namespace
 
 // --------------------------------------------------------------------------
 // host driver
 // --------------------------------------------------------------------------
+
+// PCFM_SEG_LDSROW=0: every scatter on the transposing engine (seg_rows + unit
+// gather + partial sums) -- the A/B switch of the LDS-row apply, read once.
+inline bool seg_ldsrow_enabled() {
+  static const bool on = [] {
+    const char* e = std::getenv("PCFM_SEG_LDSROW");
+    return !(e != nullptr && e[0] == '0');
+  }();
+  return on;
+}
 
 // Upper bound of work units per batch element: one per tile plus one per
 // kItems of range items (an item lies in at most 2 tiles per stencil column).
@@ -807,6 +1017,13 @@ template <int TAPS>
 inline int seg_apply(const float* in, const SegPlan& w, bool avg, int r, int B, int C, int n,
                      int V, float* out, const SegApplyWs& aw, hipStream_t st) {
   if (C == 0) return PCFM_OK;
+  if (TAPS == 1 && n <= kLdsRowMaxItems && seg_ldsrow_enabled()) {
+    const int e = allow_big_lds((const void*)seg_ldsrow1_kernel);
+    if (e) return e;
+    hipLaunchKernelGGL(seg_ldsrow1_kernel, dim3(C, B), dim3(kRowThreads), seg_ldsrow_lds(n), st,
+                       in, w.rank, w.start, avg ? 1 : 0, C, n, V, out);
+    return PCFM_OK;
+  }
   const int tiles = seg_tiles(V), umax = seg_umax(n, V, TAPS), slots = umax - tiles;
   if (n > 0)
     hipLaunchKernelGGL(seg_rows_kernel,

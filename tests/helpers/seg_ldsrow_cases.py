@@ -1,0 +1,210 @@
+"""Shapes, seeded inputs and runners of tests/test_gpu_seg_ldsrow.py.
+
+The test imports this module for the process's own path (the LDS-row apply of
+csrc/segsum.hpp where the item row fits) and runs it as a script in a child
+process with PCFM_SEG_LDSROW=0 (the switch is read once per process), which
+writes the transposing engine's results of the same cases to an .npz.
+
+Every result is computed into a NaN-filled output through the C ABI directly
+(pcfm.ops allocates its outputs itself), so a voxel the kernels leave unwritten
+shows as a NaN.
+"""
+import os
+import sys
+
+import numpy as np
+
+# csrc/segsum.hpp kLdsRowMaxItems: the longest item row the LDS-row apply takes
+LDS_ROW_MAX_ITEMS = 40000
+
+# name: (b, c, n, r, layout)
+VOX = {
+    "small": (3, 5, 1000, 4, "uniform"),
+    "ragged": (2, 70, 4097, 8, "uniform"),
+    "crowded": (1, 64, 20000, 2, "uniform"),      # ~2,500 points per cell
+    "one_voxel": (2, 3, 777, 8, "one_voxel"),
+    "empty": (1, 4, 0, 4, "uniform"),
+    "sparse": (2, 8, 300, 16, "uniform"),         # mostly empty voxels
+    "clustered": (2, 6, 6000, 8, "clustered"),    # crowded and sparse tiles in one row
+    "fit_below": (1, 2, LDS_ROW_MAX_ITEMS, 4, "uniform"),
+    "fit_above": (1, 2, LDS_ROW_MAX_ITEMS + 1, 4, "uniform"),
+}
+# name: (b, c, n, r, layout): the B, C, n of VOX at r = 2, 8, 16.  The 20000-point
+# cloud goes with r = 16, not r = 2: at r = 2 every voxel is an fp32 sum of all
+# 20000 weighted terms (partial sums ~40, half an ulp 1.9e-6), where the oracle's
+# own sequential rounding, ~sqrt(n) half-ulps = 2.7e-4, is above the bar of
+# 1e-6 * max|gx| = 9e-5 it is the reference for.
+DEVOX = {
+    "small": (3, 5, 1000, 2, "inside"),
+    "ragged": (2, 70, 4097, 8, "inside"),
+    "crowded": (1, 64, 20000, 16, "inside"),
+    "one_cell": (2, 3, 777, 8, "one_cell"),
+    "empty": (1, 4, 0, 8, "inside"),
+    "sparse": (2, 8, 300, 16, "inside"),
+    "outside": (2, 6, 3000, 8, "outside"),        # ~30 % outside [0, r-1], below it too
+    "fit_below": (1, 2, LDS_ROW_MAX_ITEMS, 4, "inside"),
+    "fit_above": (1, 2, LDS_ROW_MAX_ITEMS + 1, 4, "inside"),
+}
+FP64_CASES = ("small", "one_voxel", "one_cell", "empty", "sparse", "outside")
+
+
+def _seed(kind, name):
+    return [1 + (kind == "devox"), sum(ord(ch) for ch in name)]
+
+
+def vox_inputs(name):
+    """(feat (b, c, n) f32, coords (b, 3, n) i32, r).  fit_above is fit_below
+    plus one more point."""
+    b, c, n, r, layout = VOX[name]
+    if name == "fit_above":
+        feat, coords, _ = vox_inputs("fit_below")
+        g = np.random.default_rng(_seed("vox", name))
+        feat = np.concatenate([feat, g.standard_normal((b, c, 1)).astype(np.float32)], axis=2)
+        coords = np.concatenate([coords, g.integers(0, r, (b, 3, 1)).astype(np.int32)], axis=2)
+        return np.ascontiguousarray(feat), np.ascontiguousarray(coords), r
+    g = np.random.default_rng(_seed("vox", name))
+    feat = g.standard_normal((b, c, n)).astype(np.float32)
+    if layout == "uniform":
+        coords = g.integers(0, r, (b, 3, n)).astype(np.int32)
+    elif layout == "one_voxel":
+        coords = np.full((b, 3, n), r // 2, np.int32)
+    else:
+        coords = np.clip(np.round(g.normal(r / 2, r / 8, (b, 3, n))), 0, r - 1).astype(np.int32)
+    return feat, coords, r
+
+
+def devox_inputs(name):
+    """(grad_y (b, c, n) f32, pts (b, 3, n) f32, r)."""
+    b, c, n, r, layout = DEVOX[name]
+    if name == "fit_above":
+        gy, pts, _ = devox_inputs("fit_below")
+        g = np.random.default_rng(_seed("devox", name))
+        gy = np.concatenate([gy, g.standard_normal((b, c, 1)).astype(np.float32)], axis=2)
+        pts = np.concatenate([pts, (g.random((b, 3, 1)) * (r - 1)).astype(np.float32)], axis=2)
+        return np.ascontiguousarray(gy), np.ascontiguousarray(pts), r
+    g = np.random.default_rng(_seed("devox", name))
+    gy = g.standard_normal((b, c, n)).astype(np.float32)
+    if layout == "inside":
+        pts = (g.random((b, 3, n)) * (r - 1)).astype(np.float32)
+        if n >= 8:  # integer coordinates and the upper boundary (hi == lo)
+            pts[:, :, : n // 8] = np.round(pts[:, :, : n // 8])
+            pts[:, :, -1] = r - 1
+    elif layout == "one_cell":
+        pts = np.broadcast_to(np.array([2.25, 3.5, 4.75], np.float32)[None, :, None],
+                              (b, 3, n)).copy()
+    else:
+        pts = (g.random((b, 3, n)) * (r + 3) - 1.5).astype(np.float32)
+    return gy, pts, r
+
+
+def _cu(a):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(a)).to("cuda")
+
+
+def _nan(shape):
+    import torch
+    return torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")
+
+
+def run_vox(name):
+    """{"out", "out_planned", "ind", "cnt"} as numpy; asserts that a second call
+    of each entry returns the same bits."""
+    import torch
+    from pcfm import _lib, ops
+    feat, coords, r = vox_inputs(name)
+    b, c, n = feat.shape
+    s = r ** 3
+    f, vc = _cu(feat), _cu(coords)
+    st = torch.cuda.current_stream().cuda_stream
+    res = {}
+    outs = []
+    for _ in range(2):
+        out = _nan((b, c, s))
+        ind = torch.empty((b, n), dtype=torch.int32, device="cuda")
+        cnt = torch.empty((b, s), dtype=torch.int32, device="cuda")
+        ws = ops._workspace(_lib.query("pcfm_avg_voxelize_fwd_workspace_bytes", b, c, n, r), f)
+        _lib.call("pcfm_avg_voxelize_fwd", f.data_ptr(), vc.data_ptr(), b, c, n, r,
+                  out.data_ptr(), ind.data_ptr(), cnt.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        outs.append(out)
+    assert torch.equal(outs[0], outs[1]), f"vox {name}: two unplanned calls differ"
+    res["out"], res["ind"], res["cnt"] = outs[0], ind, cnt
+    plan = ops.avg_voxelize_plan(vc, r)
+    assert torch.equal(plan.ind, ind) and torch.equal(plan.cnt, cnt)
+    outs = []
+    for _ in range(2):
+        out = _nan((b, c, s))
+        ws = ops._workspace(_lib.query("pcfm_seg_apply_workspace_bytes", b, c, n, r, 1), f)
+        _lib.call("pcfm_avg_voxelize_fwd_planned", f.data_ptr(), plan.buf.data_ptr(), b, c, n, r,
+                  out.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        outs.append(out)
+    assert torch.equal(outs[0], outs[1]), f"vox {name}: two planned calls differ"
+    res["out_planned"] = outs[0]
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def run_devox(name):
+    """{"gx", "gx_planned", "inds", "wgts", "fwd"}: the backward of grad_y both
+    ways, the forward's stored corners and the forward of a seeded grid (for the
+    adjoint check)."""
+    import torch
+    from pcfm import _lib, ops
+    gy, pts, r = devox_inputs(name)
+    b, c, n = gy.shape
+    s = r ** 3
+    g, p = _cu(gy), _cu(pts)
+    grid = _cu(devox_grid(name))
+    fwd, inds, wgts = ops.trilinear_devoxelize_forward(r, True, p, grid)
+    st = torch.cuda.current_stream().cuda_stream
+    outs = []
+    for _ in range(2):
+        gx = _nan((b, c, s))
+        ws = ops._workspace(
+            _lib.query("pcfm_trilinear_devoxelize_bwd_workspace_bytes", b, c, n, r), g)
+        _lib.call("pcfm_trilinear_devoxelize_bwd", g.data_ptr(), inds.data_ptr(), wgts.data_ptr(),
+                  b, c, n, r, gx.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        outs.append(gx)
+    assert torch.equal(outs[0], outs[1]), f"devox {name}: two unplanned calls differ"
+    res = {"gx": outs[0], "inds": inds, "wgts": wgts, "fwd": fwd}
+    plan = ops.trilinear_devoxelize_backward_plan(inds, wgts, r)
+    outs = []
+    for _ in range(2):
+        gx = _nan((b, c, s))
+        ws = ops._workspace(_lib.query("pcfm_seg_apply_workspace_bytes", b, c, n, r, 8), g)
+        _lib.call("pcfm_trilinear_devoxelize_bwd_planned", g.data_ptr(), plan.buf.data_ptr(), b, c,
+                  n, r, gx.data_ptr(), ws.data_ptr(), ws.numel(), st)
+        outs.append(gx)
+    assert torch.equal(outs[0], outs[1]), f"devox {name}: two planned calls differ"
+    res["gx_planned"] = outs[0]
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in res.items()}
+
+
+def devox_grid(name):
+    b, c, _, r, _ = DEVOX[name]
+    g = np.random.default_rng(_seed("devox", name) + [7])
+    return g.standard_normal((b, c, r ** 3)).astype(np.float32)
+
+
+def run_all():
+    res = {}
+    for name in VOX:
+        for k, v in run_vox(name).items():
+            res[f"vox.{name}.{k}"] = v
+    for name in DEVOX:
+        for k, v in run_devox(name).items():
+            res[f"devox.{name}.{k}"] = v
+    return res
+
+
+if __name__ == "__main__":
+    here = os.path.dirname(os.path.abspath(__file__))
+    repo = os.path.dirname(os.path.dirname(here))
+    for p in (repo, os.path.join(repo, "point-cloud-flow-matching_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    out = run_all()
+    keep = {k: v for k, v in out.items() if k.rsplit(".", 1)[1] in ("out", "out_planned", "gx",
+                                                                   "gx_planned")}
+    np.savez(sys.argv[1], **keep)
