@@ -23,6 +23,7 @@
 // No culled search: brute force at 8 x 20000^2, D = 6 is 2 * 8 * 20000^2 * 13
 // lane-operations.
 #include "pcfm_common.hpp"
+#include "sqdist_nd.hpp"  // sqdist_nd<D>, group_of: shared with chamfer_cross.hip
 
 #include "../../include/pcfm_chamfer_nd.h"
 
@@ -35,25 +36,8 @@ constexpr int kQ = 8;          // queries per lane
 constexpr int kThreads = 256;  // 4 waves
 constexpr int kPerBlock = kQ * kThreads;
 
-constexpr int group_of(int d) { return d <= 3 ? 8 : 4; }
-
 __device__ __forceinline__ unsigned long long pack_key(float d, int idx) {
   return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)idx;
-}
-
-// c, q: D components each; the chain of the file comment
-template <int D>
-__device__ __forceinline__ float sqdist_nd(const float* c, const float* q) {
-  const float d1 = c[1] - q[1];
-  float acc = d1 * d1;
-  const float d0 = c[0] - q[0];
-  acc = __builtin_fmaf(d0, d0, acc);
-#pragma unroll
-  for (int k = 2; k < D; ++k) {
-    const float dk = c[k] - q[k];
-    acc = __builtin_fmaf(dk, dk, acc);
-  }
-  return acc;
 }
 
 // grid = (query blocks, splits, 2*b).  Per query only each group's minimum

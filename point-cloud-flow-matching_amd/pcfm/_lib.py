@@ -168,6 +168,18 @@ ND_SIGNATURES = {
 
 ND_ABI_VERSION = 1
 
+# name -> (restype, argtypes); every symbol of include/pcfm_chamfer_cross.h (the
+# set-against-set Chamfer means behind pcfm.metrics: a second sibling header with
+# its own version, disjoint from the two tables above)
+CROSS_SIGNATURES = {
+    "pcfm_chamfer_cross_abi_version": (_I, []),
+    "pcfm_chamfer_cross_supported": (_I, [_I]),
+    "pcfm_chamfer_cross_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
+    "pcfm_chamfer_cross_fwd": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+}
+
+CROSS_ABI_VERSION = 1
+
 _lock = threading.Lock()
 _lib = None
 
@@ -189,7 +201,7 @@ def load() -> ctypes.CDLL:
                     "`python -c 'import __graft_entry__ as g; g.build()'` "
                     "(HIP tensors have no fallback)")
             lib = ctypes.CDLL(LIB_PATH)
-            for table in (SIGNATURES, ND_SIGNATURES):
+            for table in (SIGNATURES, ND_SIGNATURES, CROSS_SIGNATURES):
                 for name, (res, args) in table.items():
                     fn = getattr(lib, name)
                     fn.restype = res
@@ -201,6 +213,10 @@ def load() -> ctypes.CDLL:
             if v != ND_ABI_VERSION:
                 raise RuntimeError(f"pcfm: chamfer_nd ABI version {v} != expected "
                                    f"{ND_ABI_VERSION}; rebuild")
+            v = lib.pcfm_chamfer_cross_abi_version()
+            if v != CROSS_ABI_VERSION:
+                raise RuntimeError(f"pcfm: chamfer_cross ABI version {v} != expected "
+                                   f"{CROSS_ABI_VERSION}; rebuild")
             _lib = lib
     return _lib
 

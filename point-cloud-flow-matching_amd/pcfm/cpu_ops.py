@@ -31,7 +31,7 @@ __all__ = [
     "avg_voxelize_forward", "avg_voxelize_backward", "trilinear_devoxelize_forward",
     "trilinear_devoxelize_backward", "ball_query", "grouping_forward", "grouping_backward",
     "chamfer_forward", "chamfer_backward", "approxmatch_forward", "matchcost_forward",
-    "matchcost_backward", "chamfer_nd_forward", "chamfer_nd_backward",
+    "matchcost_backward", "chamfer_nd_forward", "chamfer_nd_backward", "chamfer_cross_forward",
 ]
 
 # rows of the query set per pairwise block (bounds the (rows, M) temporaries)
@@ -268,6 +268,24 @@ def chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1,
 # point dimension is read from the tensors
 chamfer_nd_forward = chamfer_forward
 chamfer_nd_backward = chamfer_backward
+
+
+def chamfer_cross_forward(a: torch.Tensor, b: torch.Tensor):
+    """Every cloud of a (S, N, D) against every cloud of b (R, M, D) -> (ab, ba),
+    each (S, R) float32 (include/pcfm_chamfer_cross.h): the minima of _nn (the
+    float32 chain), their float64 sum divided by the point count in float64, one
+    rounding to float32.  An empty cloud gives 0."""
+    s, n, _ = a.shape
+    r, m, _ = b.shape
+    ab = torch.zeros((s, r), dtype=torch.float32)
+    ba = torch.zeros((s, r), dtype=torch.float32)
+    if n == 0 or m == 0 or r == 0:
+        return ab, ba
+    for i in range(s):
+        ai = a[i:i + 1].expand(r, n, -1)
+        ab[i] = (_nn(ai, b)[0].double().sum(dim=1) / n).float()
+        ba[i] = (_nn(b, ai)[0].double().sum(dim=1) / m).float()
+    return ab, ba
 
 
 # ---------------------------------------------------------------------------

@@ -1,0 +1,178 @@
+"""Generation metrics between a set of generated clouds and a set of reference
+clouds: minimum matching distance (MMD), coverage (COV) and 1-nearest-neighbour
+accuracy (1-NNA), under Chamfer distance and under the approximate EMD.
+
+Every one of them reduces an (S, R) matrix of cloud-to-cloud distances:
+
+  * pairwise_chamfer -- one launch of the set-against-set kernel
+    (csrc/chamfer_cross.hip through ops.chamfer_cross_forward): no cloud is
+    copied and no per-point distance is written;
+  * pairwise_emd -- the approximate-match cost of PyTorchEMD over gathered
+    chunks of pairs (ops.approxmatch_cost_forward, no match matrix written).
+
+Rows are generated clouds, columns reference clouds.  Nothing here needs a
+gradient: everything runs under torch.no_grad(), and every output is on the
+inputs' device (HIP tensors take the kernels, CPU tensors pcfm.cpu_ops).
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _lib, ops
+
+__all__ = ["pairwise_chamfer", "pairwise_emd", "mmd_cov", "one_nna", "generation_metrics"]
+
+# pairs per approxmatch call, at most (the batch is a grid dimension of its kernels)
+_EMD_MAX_PAIRS = 32767
+
+
+@torch.no_grad()
+def pairwise_chamfer(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """x (S, N, D), y (R, M, D) float32, D in {2, 3, 5, 6} -> (S, R) float32:
+    entry [i, j] = mean_p min_q |y[j][q] - x[i][p]|^2 + mean_q min_p |x[i][p] - y[j][q]|^2,
+    which for one pair is pcfm.sample.chamfer_l2."""
+    ab, ba = ops.chamfer_cross_forward(x.contiguous(), y.contiguous())
+    return ab + ba
+
+
+def _emd_chunk_bytes(pairs: int, n: int, m: int, like: torch.Tensor) -> int:
+    """Bytes one approxmatch call over `pairs` gathered pairs holds besides its
+    (pairs,) result: the gathered inputs and the kernels' workspace (HIP) or the
+    four (pairs, n, m) temporaries of cpu_ops.approxmatch_forward (CPU)."""
+    inputs = pairs * (n + m) * 3 * 4
+    if like.is_cuda:
+        return inputs + _lib.query("pcfm_emd_workspace_bytes", pairs, n, m, 4)
+    return inputs + 4 * pairs * n * m * 4
+
+
+def _emd_pairs_per_chunk(total: int, n: int, m: int, max_bytes: int, like: torch.Tensor) -> int:
+    """Pairs per chunk (<= total, <= _EMD_MAX_PAIRS): the largest count a bisection
+    finds whose bytes stay under max_bytes."""
+    if _emd_chunk_bytes(1, n, m, like) > max_bytes:
+        raise ValueError(f"pairwise_emd: max_bytes = {max_bytes} is below one pair's "
+                         f"{_emd_chunk_bytes(1, n, m, like)} bytes")
+    lo, hi = 1, max(1, min(total, _EMD_MAX_PAIRS))   # bytes grow with the pair count
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if _emd_chunk_bytes(mid, n, m, like) <= max_bytes:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+@torch.no_grad()
+def pairwise_emd(x: torch.Tensor, y: torch.Tensor, max_bytes: int = 1 << 30) -> torch.Tensor:
+    """x (S, n, 3), y (R, n, 3) float32 -> (S, R) float32: entry [i, j] = the
+    approximate-match cost with xyz1 = x[i], xyz2 = y[j] (PyTorchEMD's forward),
+    divided by n.
+
+    ORIENTATION: the approximate match is not symmetric in its two clouds --
+    pairwise_emd(x, x) is not a symmetric matrix (entries [i, j] and [j, i]
+    differ by more than a tenth of the largest entry on random clouds), and
+    pairwise_emd(y, x) is not the transpose of pairwise_emd(x, y).  The first
+    argument's clouds are always xyz1; nothing is symmetrised.
+
+    Pairs are gathered in chunks; a chunk's gathered inputs plus the call's
+    workspace stay under max_bytes.  The result does not depend on the chunking.
+    Anything but D = 3 and equal point counts raises ValueError."""
+    if x.dim() != 3 or y.dim() != 3 or x.shape[2] != 3 or y.shape[2] != 3:
+        raise ValueError(f"pairwise_emd: expected (S, n, 3) and (R, n, 3), got {tuple(x.shape)} "
+                         f"and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"pairwise_emd: point counts differ ({x.shape[1]} and {y.shape[1]})")
+    x, y = x.contiguous(), y.contiguous()
+    s, r, n = x.shape[0], y.shape[0], x.shape[1]
+    out = torch.empty(s * r, dtype=torch.float32, device=x.device)
+    if s * r == 0 or n == 0:
+        return out.zero_().view(s, r)
+    chunk = _emd_pairs_per_chunk(s * r, n, n, max_bytes, x)
+    for p0 in range(0, s * r, chunk):
+        p = torch.arange(p0, min(p0 + chunk, s * r), device=x.device)
+        i, j = torch.div(p, r, rounding_mode="floor"), p % r
+        _, cost = ops.approxmatch_cost_forward(x[i], y[j], want_match=False)
+        out[p0:p0 + p.numel()] = cost / n
+    return out.view(s, r)
+
+
+def _argmin_first(m: torch.Tensor, dim: int) -> torch.Tensor:
+    """argmin along dim, the LOWEST index among equal minima."""
+    lo = m.min(dim=dim, keepdim=True).values
+    shape = [1, 1]
+    shape[dim] = m.shape[dim]
+    pos = torch.arange(m.shape[dim], device=m.device).view(shape)
+    return torch.where(m == lo, pos, m.shape[dim]).min(dim=dim).values
+
+
+def _share(flags: torch.Tensor, dtype) -> torch.Tensor:
+    """Share of true entries as a 0-dim `dtype` tensor: an exact count and one
+    float64 tensor-by-tensor division, rounded once, so that HIP and CPU give the
+    same bits (a mean's rounding depends on the device's reduction, and a division
+    by a Python scalar multiplies by a rounded reciprocal on the device)."""
+    total = torch.tensor(float(flags.numel()), dtype=torch.float64, device=flags.device)
+    return (flags.sum(dtype=torch.float64) / total).to(dtype)
+
+
+@torch.no_grad()
+def mmd_cov(m: torch.Tensor) -> dict:
+    """m (S, R): rows generated clouds, columns reference clouds ->
+      mmd      mean over the columns of the column minimum (each reference cloud's
+               nearest generated cloud);
+      mmd_smp  mean over the rows of the row minimum;
+      cov      (distinct columns that are some row's argmin) / R.
+    Ties: the lowest index."""
+    if m.dim() != 2 or m.shape[0] == 0 or m.shape[1] == 0:
+        raise ValueError(f"mmd_cov: expected a non-empty (S, R) matrix, got {tuple(m.shape)}")
+    hit = torch.zeros(m.shape[1], dtype=torch.bool, device=m.device)
+    hit[_argmin_first(m, 1)] = True
+    return {"mmd": m.min(dim=0).values.mean(), "mmd_smp": m.min(dim=1).values.mean(),
+            "cov": _share(hit, m.dtype)}
+
+
+@torch.no_grad()
+def one_nna(mxx: torch.Tensor, mxy: torch.Tensor, myy: torch.Tensor) -> dict:
+    """Leave-one-out 1-nearest-neighbour classification of the S generated
+    (label 1) and R reference (label 0) clouds over
+        J = [[mxx, mxy], [mxy^T, myy]]   with +inf on the diagonal:
+    a column's prediction is the label of its argmin row (lowest index on ties) ->
+      acc      share of the columns whose prediction equals their label;
+      acc_gen  the same share among the S generated clouds;
+      acc_ref  among the R reference clouds.
+    0.5 is the aim (the sets cannot be told apart), 1.0 the worst."""
+    s, r = mxy.shape
+    if tuple(mxx.shape) != (s, s) or tuple(myy.shape) != (r, r) or s == 0 or r == 0:
+        raise ValueError(f"one_nna: expected (S, S), (S, R), (R, R), got {tuple(mxx.shape)}, "
+                         f"{tuple(mxy.shape)}, {tuple(myy.shape)}")
+    j = torch.cat([torch.cat([mxx, mxy], dim=1), torch.cat([mxy.t(), myy], dim=1)], dim=0)
+    j = j.clone()
+    j.fill_diagonal_(float("inf"))
+    label = torch.cat([torch.ones(s, device=j.device), torch.zeros(r, device=j.device)])
+    ok = label[_argmin_first(j, 0)] == label
+    return {"acc": _share(ok, mxy.dtype), "acc_gen": _share(ok[:s], mxy.dtype),
+            "acc_ref": _share(ok[s:], mxy.dtype)}
+
+
+@torch.no_grad()
+def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True) -> dict:
+    """sample (S, N, D), ref (R, M, D) float32 -> {mmd_cd, mmd_smp_cd, cov_cd,
+    1nna_cd, 1nna_gen_cd, 1nna_ref_cd} and, with emd=True, the same six with
+    _emd.  Chamfer runs over all D components (D in {2, 3, 5, 6}); EMD over the
+    first three (xyz) and needs N == M.  The S x S and R x R matrices of 1-NNA
+    come from the same kernels, a set against itself."""
+    sample, ref = sample.contiguous(), ref.contiguous()
+
+    def reduce(pairwise, a, b, tag):
+        mxy = pairwise(a, b)
+        out = {f"{k}_{tag}": v for k, v in mmd_cov(mxy).items()}
+        nna = one_nna(pairwise(a, a), mxy, pairwise(b, b))
+        out.update({f"1nna_{tag}": nna["acc"], f"1nna_gen_{tag}": nna["acc_gen"],
+                    f"1nna_ref_{tag}": nna["acc_ref"]})
+        return out
+
+    out = reduce(pairwise_chamfer, sample, ref, "cd")
+    if emd:
+        if sample.shape[-1] < 3 or ref.shape[-1] < 3:
+            raise ValueError("generation_metrics: EMD needs at least three components (xyz)")
+        out.update(reduce(pairwise_emd, sample[..., :3].contiguous(), ref[..., :3].contiguous(),
+                          "emd"))
+    return out

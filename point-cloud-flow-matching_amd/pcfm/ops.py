@@ -706,6 +706,35 @@ chamfer_6D = _chamfer_nd_namespace(6)
 
 
 # --------------------------------------------------------------------------
+# set-against-set Chamfer means (include/pcfm_chamfer_cross.h,
+# csrc/chamfer_cross.hip): what pcfm.metrics reduces.  No reference module has
+# this name; the contract is the header's.
+# --------------------------------------------------------------------------
+def chamfer_cross_forward(a: torch.Tensor, b: torch.Tensor):
+    """a (S, N, D), b (R, M, D) float32, D in {2, 3, 5, 6} -> (ab, ba), each (S, R)
+    float32: ab[i, j] = mean over the points of a[i] of the squared distance to the
+    nearest point of b[j], ba[i, j] = the same from the points of b[j] to a[i].
+    `a is b` is allowed (a set against itself)."""
+    host = _host(a, b)
+    for t, nm in ((a, "a"), (b, "b")):
+        (_check_host if host else _check)(t, nm, "f")
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != b.shape[2]:
+        raise RuntimeError(f"expected (S, N, D) and (R, M, D), got {tuple(a.shape)} and "
+                           f"{tuple(b.shape)}")
+    (s, n, d), (r, m) = a.shape, b.shape[:2]
+    if d not in (2, 3, 5, 6):
+        raise RuntimeError(f"unsupported point dimension {d}")
+    if host:
+        return cpu_ops.chamfer_cross_forward(a, b)
+    ab = torch.empty((s, r), dtype=torch.float32, device=a.device)
+    ba = torch.empty((s, r), dtype=torch.float32, device=a.device)
+    ws = _workspace(_lib.query("pcfm_chamfer_cross_workspace_bytes", s, r, n, m, d), a)
+    _lib.call("pcfm_chamfer_cross_fwd", _ptr(a), _ptr(b), s, r, n, m, d, _ptr(ab), _ptr(ba),
+              _ptr(ws), ws.numel(), _stream(a))
+    return ab, ba
+
+
+# --------------------------------------------------------------------------
 # emd_cuda (PyTorchEMD/cuda/emd.cpp:8-27): float and double
 # --------------------------------------------------------------------------
 def _emd_check(xyz1, xyz2):
