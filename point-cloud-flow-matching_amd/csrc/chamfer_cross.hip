@@ -2,22 +2,21 @@
 // points, D in {2, 3, 5, 6} (include/pcfm_chamfer_cross.h): the S x R matrices
 // the generation metrics reduce (pcfm/metrics.py).
 //
-// The search is nn_nd_kernel's (csrc/chamfer_nd.hip) without everything a mean
-// does not need -- no index, no candidate split, no key merge:
+// The search is nn_kernel's (csrc/chamfer_nd.hip), over the same query load and
+// candidate walk (csrc/chamfer_search.hpp), without everything a mean does not
+// need -- no index, no candidate split, no key merge:
 //   * a block owns kPerBlock = 2048 queries of ONE cloud, 8 per lane in
 //     registers, and walks a tile of consecutive partner clouds of the other set;
-//   * a partner's points arrive as wave-uniform grouped loads (scalar loads: the
-//     VALU reads them from SGPRs), the next group prefetched;
 //   * after each partner the block adds its minima in float64 in a fixed order
 //     (a lane's 8 queries in order, the wave's 64 lanes by xor-butterfly, the 4
 //     waves in wave order) and thread 0 stores the mean (one query block per
 //     cloud) or the block's partial sum (more: cross_finalize_kernel adds the
 //     partials in block order);
 //   * both directions are one launch; the pairs are on grid.x.
-// The minima are the fp32 values of pcfm_chamfer_nd_fwd (sqdist_nd.hpp; a min
-// does not depend on the order its operands arrive in).
+// The minima are the fp32 values of pcfm_chamfer_nd_fwd (sqdist_nd; a min does
+// not depend on the order its operands arrive in).
 #include "pcfm_common.hpp"
-#include "sqdist_nd.hpp"
+#include "chamfer_search.hpp"
 
 #include "../../include/pcfm_chamfer_cross.h"
 
@@ -26,10 +25,7 @@
 namespace pcfm {
 namespace {
 
-constexpr int kQ = 8;          // queries per lane
-constexpr int kThreads = 256;  // 4 waves
 constexpr int kWaves = kThreads / 64;
-constexpr int kPerBlock = kQ * kThreads;
 constexpr int kTileMax = 8;    // partner clouds per block, at most
 
 // grid.x = the items of direction 0 (queries a_i, partners b_j -> ab) then of
@@ -63,15 +59,7 @@ __global__ void __launch_bounds__(kThreads)
   const int qbase = qblk * kPerBlock;
 
   float qv[kQ][D];
-#pragma unroll
-  for (int q = 0; q < kQ; ++q) {
-    const int j = qbase + q * kThreads + threadIdx.x;
-    const int jj = j < nq ? j : nq - 1;  // a ragged tail reads the last point, and is not summed
-    const float* p = qp + ((size_t)qc * nq + jj) * D;
-#pragma unroll
-    for (int e = 0; e < D; ++e) qv[q][e] = p[e];
-  }
-  const int kg1 = nc / kG * kG;
+  load_queries<D>(qp + (size_t)qc * nq * D, nq, qbase, qv);  // a ragged tail is not summed
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 
   for (int pc = p0; pc < p1; ++pc) {
@@ -79,7 +67,7 @@ __global__ void __launch_bounds__(kThreads)
     float best[kQ];
 #pragma unroll
     for (int q = 0; q < kQ; ++q) best[q] = __builtin_inff();
-    auto group = [&](const float (&c)[D * kG], int valid) {
+    walk_candidates<D>(cb, 0, nc, [&](const float (&c)[D * kG], int, int valid) {
 #pragma unroll
       for (int q = 0; q < kQ; ++q) {
 #pragma unroll
@@ -89,27 +77,7 @@ __global__ void __launch_bounds__(kThreads)
           best[q] = __builtin_fminf(best[q], d);
         }
       }
-    };
-    int k = 0;
-    if (k < kg1) {
-      float c[D * kG], nx[D * kG];
-#pragma unroll
-      for (int e = 0; e < D * kG; ++e) c[e] = cb[e];
-      for (; k < kg1; k += kG) {
-        const int kn = k + kG < kg1 ? k + kG : k;
-#pragma unroll
-        for (int e = 0; e < D * kG; ++e) nx[e] = cb[(size_t)D * kn + e];
-        group(c, kG);
-#pragma unroll
-        for (int e = 0; e < D * kG; ++e) c[e] = nx[e];
-      }
-    }
-    if (k < nc) {  // ragged tail: one partial group, loads clamped to the last candidate
-      float c[D * kG];
-#pragma unroll
-      for (int e = 0; e < D * kG; ++e) c[e] = cb[(size_t)D * min(k + e / D, nc - 1) + e % D];
-      group(c, nc - k);
-    }
+    });
 
     // the block's sum, float64, fixed order
     double acc = 0.0;

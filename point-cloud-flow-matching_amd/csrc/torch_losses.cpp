@@ -3,7 +3,8 @@
 // module is built under both names: the reference's setup.py and backend.py
 // build `emd_ext`, PyTorchEMD/setup.py:26-29 and backend.py:11-12, and emd.py
 // imports it as emd_cuda).  -DPCFM_TORCH_MODULE=3 -DPCFM_CHAMFER_DIM=k builds
-// chamfer_2D / chamfer_5D / chamfer_6D over include/pcfm_chamfer_nd.h.
+// chamfer_2D / chamfer_5D / chamfer_6D over include/pcfm_chamfer_nd.h, from the
+// same forward / backward as module 1.
 //
 // chamfer_3D replaces third_party/ChamferDistancePytorch/chamfer3D/chamfer_cuda.cpp:17-32
 // (forward / backward into caller-allocated tensors, int status: 1 ok, 0 after
@@ -60,83 +61,36 @@ at::Tensor workspace(size_t bytes, const at::Tensor& like) {
   return at::empty({(int64_t)std::max<size_t>(bytes, 1)}, like.options().dtype(at::kByte));
 }
 
+#if PCFM_TORCH_MODULE == 1 || PCFM_TORCH_MODULE == 3
+// One forward / backward for chamfer_3D and chamfer_2D / chamfer_5D / chamfer_6D
+// (ChamferDistancePytorch/chamfer{2,3,5,6}D/chamfer_cuda.cpp:17-32).
 #if PCFM_TORCH_MODULE == 1
-// chamfer_cuda.cpp:17-24
-int chamfer_forward(at::Tensor xyz1, at::Tensor xyz2, at::Tensor dist1, at::Tensor dist2,
-                    at::Tensor idx1, at::Tensor idx2) {
-  try {
-    check_hip(xyz1, "xyz1", at::kFloat);
-    check_hip(xyz2, "xyz2", at::kFloat);
-    check_hip(dist1, "dist1", at::kFloat);
-    check_hip(dist2, "dist2", at::kFloat);
-    check_hip(idx1, "idx1", at::kInt);
-    check_hip(idx2, "idx2", at::kInt);
-    check_shape(xyz1, "xyz1", {-1, -1, 3});
-    const int64_t B = xyz1.size(0), N = xyz1.size(1);
-    check_shape(xyz2, "xyz2", {B, -1, 3});
-    const int64_t M = xyz2.size(1);
-    check_shape(dist1, "dist1", {B, N});
-    check_shape(dist2, "dist2", {B, M});
-    check_shape(idx1, "idx1", {B, N});
-    check_shape(idx2, "idx2", {B, M});
-    for (const at::Tensor* t : {&xyz2, &dist1, &dist2, &idx1, &idx2})
-      check_same_device(xyz1, *t, "an output or xyz2");
-    const int b = xyz1.size(0), n = xyz1.size(1), m = xyz2.size(1);
-    auto ws = workspace(pcfm_chamfer_workspace_bytes(b, n, m), xyz1);
-    check_rc(pcfm_chamfer_fwd(xyz1.data_ptr<float>(), xyz2.data_ptr<float>(), b, n, m,
-                              dist1.data_ptr<float>(), dist2.data_ptr<float>(),
-                              idx1.data_ptr<int>(), idx2.data_ptr<int>(), ws.data_ptr(),
-                              (size_t)ws.numel(), stream_of(xyz1)),
-             "chamfer forward");
-  } catch (const c10::Error& e) {
-    std::printf("error in nnd updateOutput: %s\n", e.what_without_backtrace());
-    return 0;
-  }
-  return 1;
+// the 3-D entries of include/pcfm.h: brute force or the culled search
+constexpr int64_t kDim = 3;
+size_t ws_bytes(int b, int n, int m) { return pcfm_chamfer_workspace_bytes(b, n, m); }
+template <class... A>
+int fwd(const float* p1, const float* p2, int b, int n, int m, A... rest) {
+  return pcfm_chamfer_fwd(p1, p2, b, n, m, rest...);
 }
-
-// chamfer_cuda.cpp:26-32
-int chamfer_backward(at::Tensor xyz1, at::Tensor xyz2, at::Tensor gradxyz1, at::Tensor gradxyz2,
-                     at::Tensor graddist1, at::Tensor graddist2, at::Tensor idx1,
-                     at::Tensor idx2) {
-  try {
-    check_hip(xyz1, "xyz1", at::kFloat);
-    check_hip(xyz2, "xyz2", at::kFloat);
-    check_hip(gradxyz1, "gradxyz1", at::kFloat);
-    check_hip(gradxyz2, "gradxyz2", at::kFloat);
-    check_hip(graddist1, "graddist1", at::kFloat);
-    check_hip(graddist2, "graddist2", at::kFloat);
-    check_hip(idx1, "idx1", at::kInt);
-    check_hip(idx2, "idx2", at::kInt);
-    check_shape(xyz1, "xyz1", {-1, -1, 3});
-    const int64_t B = xyz1.size(0), N = xyz1.size(1);
-    check_shape(xyz2, "xyz2", {B, -1, 3});
-    const int64_t M = xyz2.size(1);
-    check_shape(gradxyz1, "gradxyz1", {B, N, 3});
-    check_shape(gradxyz2, "gradxyz2", {B, M, 3});
-    check_shape(graddist1, "graddist1", {B, N});
-    check_shape(graddist2, "graddist2", {B, M});
-    check_shape(idx1, "idx1", {B, N});
-    check_shape(idx2, "idx2", {B, M});
-    for (const at::Tensor* t : {&xyz2, &gradxyz1, &gradxyz2, &graddist1, &graddist2, &idx1, &idx2})
-      check_same_device(xyz1, *t, "a gradient, index or xyz2");
-    const int b = xyz1.size(0), n = xyz1.size(1), m = xyz2.size(1);
-    check_rc(pcfm_chamfer_bwd(xyz1.data_ptr<float>(), xyz2.data_ptr<float>(), b, n, m,
-                              graddist1.data_ptr<float>(), graddist2.data_ptr<float>(),
-                              idx1.data_ptr<int>(), idx2.data_ptr<int>(),
-                              gradxyz1.data_ptr<float>(), gradxyz2.data_ptr<float>(),
-                              stream_of(xyz1)),
-             "chamfer backward");
-  } catch (const c10::Error& e) {
-    std::printf("error in nnd get grad: %s\n", e.what_without_backtrace());
-    return 0;
-  }
-  return 1;
+template <class... A>
+int bwd(const float* p1, const float* p2, int b, int n, int m, A... rest) {
+  return pcfm_chamfer_bwd(p1, p2, b, n, m, rest...);
 }
-#elif PCFM_TORCH_MODULE == 3
-// chamfer_2D / chamfer_5D / chamfer_6D (ChamferDistancePytorch/chamfer{2,5,6}D/
-// chamfer_cuda.cpp): the chamfer_3D contract over PCFM_CHAMFER_DIM components
+#else
+// include/pcfm_chamfer_nd.h over PCFM_CHAMFER_DIM components
 constexpr int64_t kDim = PCFM_CHAMFER_DIM;
+size_t ws_bytes(int b, int n, int m) {
+  return pcfm_chamfer_nd_workspace_bytes(b, n, m, (int)kDim);
+}
+template <class... A>
+int fwd(const float* p1, const float* p2, int b, int n, int m, A... rest) {
+  return pcfm_chamfer_nd_fwd(p1, p2, b, n, m, (int)kDim, rest...);
+}
+template <class... A>
+int bwd(const float* p1, const float* p2, int b, int n, int m, A... rest) {
+  return pcfm_chamfer_nd_bwd(p1, p2, b, n, m, (int)kDim, rest...);
+}
+#endif
 
 int chamfer_forward(at::Tensor xyz1, at::Tensor xyz2, at::Tensor dist1, at::Tensor dist2,
                     at::Tensor idx1, at::Tensor idx2) {
@@ -158,11 +112,10 @@ int chamfer_forward(at::Tensor xyz1, at::Tensor xyz2, at::Tensor dist1, at::Tens
     for (const at::Tensor* t : {&xyz2, &dist1, &dist2, &idx1, &idx2})
       check_same_device(xyz1, *t, "an output or xyz2");
     const int b = xyz1.size(0), n = xyz1.size(1), m = xyz2.size(1);
-    auto ws = workspace(pcfm_chamfer_nd_workspace_bytes(b, n, m, (int)kDim), xyz1);
-    check_rc(pcfm_chamfer_nd_fwd(xyz1.data_ptr<float>(), xyz2.data_ptr<float>(), b, n, m,
-                                 (int)kDim, dist1.data_ptr<float>(), dist2.data_ptr<float>(),
-                                 idx1.data_ptr<int>(), idx2.data_ptr<int>(), ws.data_ptr(),
-                                 (size_t)ws.numel(), stream_of(xyz1)),
+    auto ws = workspace(ws_bytes(b, n, m), xyz1);
+    check_rc(fwd(xyz1.data_ptr<float>(), xyz2.data_ptr<float>(), b, n, m,
+                 dist1.data_ptr<float>(), dist2.data_ptr<float>(), idx1.data_ptr<int>(),
+                 idx2.data_ptr<int>(), ws.data_ptr(), (size_t)ws.numel(), stream_of(xyz1)),
              "chamfer forward");
   } catch (const c10::Error& e) {
     std::printf("error in nnd updateOutput: %s\n", e.what_without_backtrace());
@@ -196,11 +149,10 @@ int chamfer_backward(at::Tensor xyz1, at::Tensor xyz2, at::Tensor gradxyz1, at::
     for (const at::Tensor* t : {&xyz2, &gradxyz1, &gradxyz2, &graddist1, &graddist2, &idx1, &idx2})
       check_same_device(xyz1, *t, "a gradient, index or xyz2");
     const int b = xyz1.size(0), n = xyz1.size(1), m = xyz2.size(1);
-    check_rc(pcfm_chamfer_nd_bwd(xyz1.data_ptr<float>(), xyz2.data_ptr<float>(), b, n, m,
-                                 (int)kDim, graddist1.data_ptr<float>(),
-                                 graddist2.data_ptr<float>(), idx1.data_ptr<int>(),
-                                 idx2.data_ptr<int>(), gradxyz1.data_ptr<float>(),
-                                 gradxyz2.data_ptr<float>(), stream_of(xyz1)),
+    check_rc(bwd(xyz1.data_ptr<float>(), xyz2.data_ptr<float>(), b, n, m,
+                 graddist1.data_ptr<float>(), graddist2.data_ptr<float>(), idx1.data_ptr<int>(),
+                 idx2.data_ptr<int>(), gradxyz1.data_ptr<float>(), gradxyz2.data_ptr<float>(),
+                 stream_of(xyz1)),
              "chamfer backward");
   } catch (const c10::Error& e) {
     std::printf("error in nnd get grad: %s\n", e.what_without_backtrace());

@@ -573,55 +573,11 @@ backend = types.SimpleNamespace(
 
 
 # --------------------------------------------------------------------------
-# chamfer_3D (chamfer_cuda.cpp:17-32): caller-allocated outputs, int status
-# --------------------------------------------------------------------------
-def _chamfer_forward(xyz1, xyz2, dist1, dist2, idx1, idx2) -> int:
-    try:
-        host = _host(xyz1, xyz2, dist1, dist2, idx1, idx2)
-        for t, nm, k in ((xyz1, "xyz1", "f"), (xyz2, "xyz2", "f"), (dist1, "dist1", "f"),
-                         (dist2, "dist2", "f"), (idx1, "idx1", "i"), (idx2, "idx2", "i")):
-            (_check_host if host else _check)(t, nm, k)
-        if host:
-            cpu_ops.chamfer_forward(xyz1, xyz2, dist1, dist2, idx1, idx2)
-            return 1
-        b, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
-        ws = _workspace(_lib.query("pcfm_chamfer_workspace_bytes", b, n, m), xyz1)
-        _lib.call("pcfm_chamfer_fwd", _ptr(xyz1), _ptr(xyz2), b, n, m, _ptr(dist1), _ptr(dist2),
-                  _ptr(idx1), _ptr(idx2), _ptr(ws), ws.numel(), _stream(xyz1))
-    except RuntimeError as e:  # the reference prints and returns 0 (chamfer3D.cu:145-151)
-        print(f"error in nnd updateOutput: {e}")
-        return 0
-    return 1
-
-
-def _chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2) -> int:
-    try:
-        host = _host(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2)
-        for t, nm, k in ((xyz1, "xyz1", "f"), (xyz2, "xyz2", "f"), (gradxyz1, "gradxyz1", "f"),
-                         (gradxyz2, "gradxyz2", "f"), (graddist1, "graddist1", "f"),
-                         (graddist2, "graddist2", "f"), (idx1, "idx1", "i"), (idx2, "idx2", "i")):
-            (_check_host if host else _check)(t, nm, k)
-        if host:
-            cpu_ops.chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1,
-                                     idx2)
-            return 1
-        b, n, m = xyz1.shape[0], xyz1.shape[1], xyz2.shape[1]
-        _lib.call("pcfm_chamfer_bwd", _ptr(xyz1), _ptr(xyz2), b, n, m, _ptr(graddist1),
-                  _ptr(graddist2), _ptr(idx1), _ptr(idx2), _ptr(gradxyz1), _ptr(gradxyz2),
-                  _stream(xyz1))
-    except RuntimeError as e:
-        print(f"error in nnd get grad: {e}")
-        return 0
-    return 1
-
-
-chamfer_3D = types.SimpleNamespace(forward=_chamfer_forward, backward=_chamfer_backward)
-
-
-# --------------------------------------------------------------------------
-# chamfer_2D / chamfer_5D / chamfer_6D (ChamferDistancePytorch/chamfer{2,5,6}D/
-# chamfer_cuda.cpp): the same contract over D-component points
-# (include/pcfm_chamfer_nd.h, csrc/chamfer_nd.hip)
+# chamfer_3D (chamfer_cuda.cpp:17-32) and chamfer_2D / chamfer_5D / chamfer_6D
+# (ChamferDistancePytorch/chamfer{2,5,6}D/chamfer_cuda.cpp): caller-allocated
+# outputs, int status.  One forward and one backward; chamfer_3D is bound to the
+# 3-D C entries (include/pcfm.h: brute force or the culled search), the others
+# to the N-D ones (include/pcfm_chamfer_nd.h, csrc/chamfer_nd.hip).
 # --------------------------------------------------------------------------
 def _chamfer_nd_shapes(xyz1, xyz2, d, per_point, per_coord):
     """(b, n, m, d) after checking every extent the kernels index with."""
@@ -644,8 +600,9 @@ def _chamfer_nd_shapes(xyz1, xyz2, d, per_point, per_coord):
     return b, n, m, d
 
 
-def _chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2, d=None) -> int:
-    """Point dimension d (None: the tensors' last dimension) in {2, 3, 5, 6}."""
+def _chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2, d=None, entry="_nd") -> int:
+    """Point dimension d (None: the tensors' last dimension) in {2, 3, 5, 6};
+    entry "": the 3-D C entries (d = 3 only)."""
     try:
         host = _host(xyz1, xyz2, dist1, dist2, idx1, idx2)
         for t, nm, k in ((xyz1, "xyz1", "f"), (xyz2, "xyz2", "f"), (dist1, "dist1", "f"),
@@ -654,19 +611,20 @@ def _chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2, d=None) -> int:
         b, n, m, d = _chamfer_nd_shapes(xyz1, xyz2, d, ((dist1, "dist1", 0), (dist2, "dist2", 1),
                                                         (idx1, "idx1", 0), (idx2, "idx2", 1)), ())
         if host:
-            cpu_ops.chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2)
+            cpu_ops.chamfer_forward(xyz1, xyz2, dist1, dist2, idx1, idx2)
             return 1
-        ws = _workspace(_lib.query("pcfm_chamfer_nd_workspace_bytes", b, n, m, d), xyz1)
-        _lib.call("pcfm_chamfer_nd_fwd", _ptr(xyz1), _ptr(xyz2), b, n, m, d, _ptr(dist1),
+        dim = (d,) if entry else ()
+        ws = _workspace(_lib.query(f"pcfm_chamfer{entry}_workspace_bytes", b, n, m, *dim), xyz1)
+        _lib.call(f"pcfm_chamfer{entry}_fwd", _ptr(xyz1), _ptr(xyz2), b, n, m, *dim, _ptr(dist1),
                   _ptr(dist2), _ptr(idx1), _ptr(idx2), _ptr(ws), ws.numel(), _stream(xyz1))
-    except RuntimeError as e:
+    except RuntimeError as e:  # the reference prints and returns 0 (chamfer3D.cu:145-151)
         print(f"error in nnd updateOutput: {e}")
         return 0
     return 1
 
 
 def _chamfer_nd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2,
-                         d=None) -> int:
+                         d=None, entry="_nd") -> int:
     try:
         host = _host(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2)
         for t, nm, k in ((xyz1, "xyz1", "f"), (xyz2, "xyz2", "f"), (gradxyz1, "gradxyz1", "f"),
@@ -678,31 +636,33 @@ def _chamfer_nd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, i
                             (idx1, "idx1", 0), (idx2, "idx2", 1)),
             ((gradxyz1, "gradxyz1", 0), (gradxyz2, "gradxyz2", 1)))
         if host:
-            cpu_ops.chamfer_nd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2,
-                                        idx1, idx2)
+            cpu_ops.chamfer_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1,
+                                     idx2)
             return 1
-        _lib.call("pcfm_chamfer_nd_bwd", _ptr(xyz1), _ptr(xyz2), b, n, m, d, _ptr(graddist1),
-                  _ptr(graddist2), _ptr(idx1), _ptr(idx2), _ptr(gradxyz1), _ptr(gradxyz2),
-                  _stream(xyz1))
+        dim = (d,) if entry else ()
+        _lib.call(f"pcfm_chamfer{entry}_bwd", _ptr(xyz1), _ptr(xyz2), b, n, m, *dim,
+                  _ptr(graddist1), _ptr(graddist2), _ptr(idx1), _ptr(idx2), _ptr(gradxyz1),
+                  _ptr(gradxyz2), _stream(xyz1))
     except RuntimeError as e:
         print(f"error in nnd get grad: {e}")
         return 0
     return 1
 
 
-def _chamfer_nd_namespace(d):
+def _chamfer_namespace(d, entry):
     def forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
-        return _chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2, d)
+        return _chamfer_nd_forward(xyz1, xyz2, dist1, dist2, idx1, idx2, d, entry)
 
     def backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1, idx2):
         return _chamfer_nd_backward(xyz1, xyz2, gradxyz1, gradxyz2, graddist1, graddist2, idx1,
-                                    idx2, d)
+                                    idx2, d, entry)
     return types.SimpleNamespace(forward=forward, backward=backward)
 
 
-chamfer_2D = _chamfer_nd_namespace(2)
-chamfer_5D = _chamfer_nd_namespace(5)
-chamfer_6D = _chamfer_nd_namespace(6)
+chamfer_3D = _chamfer_namespace(3, "")
+chamfer_2D = _chamfer_namespace(2, "_nd")
+chamfer_5D = _chamfer_namespace(5, "_nd")
+chamfer_6D = _chamfer_namespace(6, "_nd")
 
 
 # --------------------------------------------------------------------------

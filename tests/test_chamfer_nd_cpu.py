@@ -208,14 +208,17 @@ def test_shipped_kernels_have_no_scratch(tmp_path):
     fwd, grad = {}, {}
     for co in codeobj.extract(_lib.LIB_PATH, str(tmp_path)):
         for name, res in codeobj.kernel_resources(co).items():
-            m = re.search(r"nn_nd_kernelILi(\d+)E", name)
-            if m:
-                assert int(m.group(1)) not in fwd, name
-                fwd[int(m.group(1))] = res
-            elif "nn_nd_grad_kernel" in name:
-                grad[name] = res
+            # one brute-force forward and one backward per D in the whole library: the 3-D
+            # entries launch the D = 3 instantiations (csrc/chamfer_search.hpp)
+            for table, kernel in ((fwd, "nn_kernel"), (grad, "nn_grad_kernel")):
+                m = re.search(r"\d%sILi(\d+)E" % kernel, name)
+                if m:
+                    assert int(m.group(1)) not in table, name
+                    table[int(m.group(1))] = res
+            # no other brute-force search or gradient kernel beside them
+            assert not re.search(r"nn_nd_|\d(nn_kernel|nn_grad_kernel)E", name), name
     assert sorted(fwd) == [2, 3, 5, 6]
-    assert len(grad) == 1
+    assert sorted(grad) == [2, 3, 5, 6]
     for k, res in list(fwd.items()) + list(grad.items()):
         assert res["scratch"] == 0, (k, res)
         assert res["wg"] == 256, (k, res)

@@ -124,6 +124,32 @@ def test_chamfer_fwd_bwd_against_oracle(b, n, m):
     _close(x2.grad, e2, rtol=1e-5, atol=1e-6)
 
 
+@pytest.mark.parametrize("bad", ["dist1 (b, n + 1)", "idx2 (b, m, 1)", "gradxyz1 (b, n, 2)",
+                                 "xyz2 another batch size"])
+def test_chamfer_3d_refuses_mis_shaped_tensors(bad, capfd):
+    """chamfer_3D checks every extent the kernels index with, as chamfer_{2,5,6}D and the
+    C++ extension do: a mis-shaped tensor prints the reference's line, returns 0 and
+    leaves every output as it was.  (The backward's graddist1 has dist1's shape; the
+    forward takes no gradxyz1.)"""
+    b, n, m = 2, 7, 5
+    xyz1 = torch.rand(b, n, 3)
+    xyz2 = torch.rand(b + (bad == "xyz2 another batch size"), m, 3)
+    f = {"dist1": (b, n + (bad == "dist1 (b, n + 1)")), "dist2": (b, m),
+         "gradxyz1": (b, n, 3 - (bad == "gradxyz1 (b, n, 2)")), "gradxyz2": (b, m, 3)}
+    i = {"idx1": (b, n), "idx2": (b, m) + ((1,) if bad == "idx2 (b, m, 1)" else ())}
+    t = {k: torch.full(s, 7.0) for k, s in f.items()}
+    t.update({k: torch.zeros(s, dtype=torch.int32) for k, s in i.items()})
+    before = {k: v.clone() for k, v in t.items()}
+    if bad != "gradxyz1 (b, n, 2)":
+        assert ops.chamfer_3D.forward(xyz1, xyz2, t["dist1"], t["dist2"], t["idx1"],
+                                      t["idx2"]) == 0
+        assert "error in nnd updateOutput: " in capfd.readouterr().out
+    assert ops.chamfer_3D.backward(xyz1, xyz2, t["gradxyz1"], t["gradxyz2"], t["dist1"],
+                                   t["dist2"], t["idx1"], t["idx2"]) == 0
+    assert "error in nnd get grad: " in capfd.readouterr().out
+    assert all(torch.equal(t[k], before[k]) for k in t)
+
+
 def test_chamfer_self_distance_is_zero():
     """README.md:116-133: CD(x, x) = 0 with idx = identity for distinct points."""
     a = RNG.standard_normal((2, 2048, 3)).astype(np.float32)

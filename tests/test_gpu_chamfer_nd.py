@@ -4,7 +4,8 @@ include/pcfm_chamfer_nd.h, pcfm.ops.chamfer_{2,5,6}D, chamfer{2,5,6}D/) against
   * the reference's chamfer_python.distChamfer fixtures (float64; indices
     exact -- tests/golden/make_chamfer_nd_golden.py asserts the gaps that make
     that safe);
-  * the oracle-checked 3-D brute-force kernel, bit for bit, at D = 3;
+  * the oracle-checked 3-D entry (pcfm_chamfer_fwd), bit for bit, at D = 3: both
+    entries launch the one D = 3 brute-force kernel;
   * the CPU backend (pcfm.cpu_ops) and the float64 gradient formula;
   * the C ABI's memory contract (the row runner of tests/test_gpu_abi_contract.py).
 
@@ -90,7 +91,7 @@ def test_vs_reference_fixtures(ops, golden, report, d):
     report(f"chamfer_nd/d{d}_max_rel_dist_dev_vs_distChamfer", worst)
 
 
-# ---- 2. D = 3: the bits of the oracle-checked 3-D brute-force kernel -----------------
+# ---- 2. D = 3: the bits of the oracle-checked 3-D entry (the same kernel) --------------
 @pytest.mark.parametrize("case", list(cases.CASES))
 def test_d3_is_bit_equal_to_the_3d_kernel(ops, case):
     a, c = (cu(t) for t in cases.inputs(case, 3))
@@ -127,6 +128,29 @@ def test_vs_cpu_backend(ops, d, b, n, m):
         assert (np_(got[0]) == 0).all() and (np_(got[2]) == 0).all()
 
 
+@pytest.mark.parametrize("d", (2, 3, 5, 6))
+@pytest.mark.parametrize("b,n,m", [(2, 70, 3), (1, 5, 1)])
+def test_fewer_candidates_than_one_group(ops, d, b, n, m):
+    """m below the candidate group (8 for D <= 3, 4 for D = 5, 6): the walk is its ragged
+    tail group alone, every load clamped to the last candidate.  Exact against the CPU
+    backend, which rounds the same chain the same way (pcfm.cpu_ops._sqdist_nd)."""
+    g = np.random.default_rng(1000 + 10 * d + m)
+    a = g.standard_normal((b, n, d)).astype(np.float32)
+    c = g.standard_normal((b, m, d)).astype(np.float32)
+    c[:, 0] = a[:, 1]                                     # an exact hit
+    exp = (torch.empty(b, n), torch.empty(b, m), torch.empty(b, n, dtype=torch.int32),
+           torch.empty(b, m, dtype=torch.int32))
+    assert ops._chamfer_nd_forward(torch.from_numpy(a), torch.from_numpy(c), *exp, d) == 1
+    entries = [lambda x, y, *o: ops._chamfer_nd_forward(x, y, *o, d)]
+    if d == 3:
+        entries.append(ops.chamfer_3D.forward)
+    for entry in entries:
+        got = outs(b, n, m)
+        assert entry(cu(a), cu(c), *got) == 1
+        for p, q in zip(got, exp):
+            np.testing.assert_array_equal(np_(p), q.numpy())
+
+
 # ---- 4. backward ----------------------------------------------------------------------
 def grad_f64(a, c, gd1, gd2, i1, i2):
     """The float64 formula with the forward's indices (numpy in, numpy out)."""
@@ -142,9 +166,16 @@ def grad_f64(a, c, gd1, gd2, i1, i2):
     return g1, g2
 
 
-@pytest.mark.parametrize("d", cases.DIMS)
+# d = 3 runs through both C entries: "3d" pcfm_chamfer_bwd, "3nd" pcfm_chamfer_nd_bwd
+@pytest.mark.parametrize("d", cases.DIMS + ("3d", "3nd"))
 @pytest.mark.parametrize("case", ["split", "ties"])
 def test_backward_vs_float64(ops, d, case):
+    if d == "3d":
+        d, backward = 3, ops.chamfer_3D.backward
+    elif d == "3nd":
+        d, backward = 3, lambda *t: ops._chamfer_nd_backward(*t, d=3)
+    else:
+        backward = getattr(ops, f"chamfer_{d}D").backward
     a, c = cases.inputs(case, d)
     b, n, m = a.shape[0], a.shape[1], c.shape[1]
     g = np.random.default_rng(d)
@@ -153,8 +184,7 @@ def test_backward_vs_float64(ops, d, case):
     s2 = g.standard_normal((b, m, d)).astype(np.float32)
     _, _, i1, i2 = forward(ops, cu(a), cu(c), d)
     g1, g2 = cu(s1), cu(s2)
-    assert getattr(ops, f"chamfer_{d}D").backward(cu(a), cu(c), g1, g2, cu(gd1), cu(gd2), i1,
-                                                  i2) == 1
+    assert backward(cu(a), cu(c), g1, g2, cu(gd1), cu(gd2), i1, i2) == 1
     e1, e2 = grad_f64(a, c, gd1, gd2, np_(i1), np_(i2))
     np.testing.assert_allclose(np_(g1), s1 + e1, **BWD_TOL)
     np.testing.assert_allclose(np_(g2), s2 + e2, **BWD_TOL)
@@ -354,9 +384,8 @@ def test_timings_recorded(ops, report, b, n, m, name):
     """d = 6 forward / backward beside the 3-D entry points in the same process:
     warm-up, HIP events, median of 7.  In this session the 3-D forward takes its
     culled search from 16M pairs (tests/conftest.py), so the brute-force
-    yardstick at the C2 shape is the D = 3 instantiation of the new kernel --
-    the same loop as the 3-D brute-force kernel, bit-equal to it (test 2); both
-    are recorded."""
+    yardstick at the C2 shape is the N-D entry at D = 3 -- the kernel the 3-D
+    entry launches below its culling threshold (test 2); both are recorded."""
     g = torch.Generator(device=DEV).manual_seed(1)
     rec = {}
     for d in (3, 6):

@@ -243,9 +243,13 @@ def test_generation_metrics_keys_and_consistency():
 # ---- 6. the shipped device code -----------------------------------------------------
 def test_shipped_cross_kernels_have_no_scratch(tmp_path):
     assert codeobj.available(), "ROCm LLVM tools absent"
-    fwd, fin = {}, {}
+    fwd, fin, brute3 = {}, {}, []
     for co in codeobj.extract(_lib.LIB_PATH, str(tmp_path)):
         for name, res in codeobj.kernel_resources(co).items():
+            # the per-point search whose query load and candidate walk cross_kernel shares
+            # (csrc/chamfer_search.hpp): exactly one D = 3 forward kernel in the library
+            if re.search(r"\dnn_kernel(ILi3E|E)|nn_nd_kernelILi3E", name):
+                brute3.append(name)
             m = re.search(r"cross_kernelILi(\d+)E", name)
             if m:
                 assert int(m.group(1)) not in fwd, name
@@ -254,6 +258,7 @@ def test_shipped_cross_kernels_have_no_scratch(tmp_path):
                 fin[name] = res
     assert sorted(fwd) == [2, 3, 5, 6]
     assert len(fin) == 1
+    assert len(brute3) == 1, brute3
     for k, res in list(fwd.items()) + list(fin.items()):
         assert res["scratch"] == 0, (k, res)
     for k, res in fwd.items():
