@@ -20,6 +20,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "bn_chan.hpp"
 #include "pcfm_common.hpp"
 
 namespace pcfm {
@@ -173,57 +174,30 @@ __device__ __forceinline__ float tap_sum(const float* __restrict__ s, const int 
 // Optional epilogue of a gather: out = scale[b, c] * sum + add[b, c, i]
 // (either pointer may be null).  Used to fold a squeeze-excitation channel
 // scale of the rows and the residual point branch into the devoxelization.
-struct RowBn;
 struct GatherEpi {
   const float* scale = nullptr;  // [B][C]
   const float* add = nullptr;    // [B][C][NI]
   // optional act(bn(.)) of the add operand (PVConv's point-branch BatchNorm1d +
   // ReLU: SharedMLP's activation is never written); mean == nullptr: plain add
-  const float* add_mean = nullptr;
-  const float* add_invstd = nullptr;
-  const float* add_gamma = nullptr;
-  const float* add_beta = nullptr;
-  float add_slope = 0.0f;
+  BnParam add_bn;
 };
+// the add operand's transform for channel c (identity when there is none)
+__device__ __forceinline__ BnChan add_bn_at(const GatherEpi& epi, int c) {
+  return epi.add_bn.at_or_identity(c);
+}
 
-// Optional transform of the rows as they are staged: row value v of channel c
-// becomes act(fma((v - mean[c]) * invstd[c], gamma[c], beta[c])) with act(t) =
-// t > 0 ? t : slope * t -- PVConv's BatchNorm3d + LeakyReLU applied to the conv
-// output while the devoxelization stages it, exactly as bn_act_apply_kernel
-// computes it (norm.hip), so the activation is never written.
-struct RowBn {
-  const float* mean = nullptr;  // nullptr: rows staged as they are
-  const float* invstd = nullptr;
-  const float* gamma = nullptr;
-  const float* beta = nullptr;
-  float slope = 0.0f;
-};
-struct RowBnC {  // one channel's constants
-  float m, is, g, bt, slope;
-  __device__ __forceinline__ float operator()(float v) const {
-    const float t = __builtin_fmaf((v - m) * is, g, bt);
-    return t > 0.0f ? t : (slope == 0.0f ? 0.0f : t * slope);
-  }
-  __device__ __forceinline__ float4 operator()(float4 v) const {
-    return make_float4((*this)(v.x), (*this)(v.y), (*this)(v.z), (*this)(v.w));
-  }
-};
-__device__ __forceinline__ RowBnC row_bn_at(const RowBn& bn, int c) {
-  return RowBnC{bn.mean[c], bn.invstd[c], bn.gamma[c], bn.beta[c], bn.slope};
-}
-// the add operand's transform for channel c (identity when epi.add_mean == nullptr)
-__device__ __forceinline__ RowBnC add_bn_at(const GatherEpi& epi, int c) {
-  if (epi.add_mean == nullptr) return RowBnC{0.0f, 1.0f, 1.0f, 0.0f, 1.0f};
-  return RowBnC{epi.add_mean[c], epi.add_invstd[c], epi.add_gamma[c], epi.add_beta[c],
-                epi.add_slope};
-}
+// Optional transform of the rows as they are staged (the kernels' `bn`
+// argument, a BnParam): row value v of channel c becomes BnChan::z(v) --
+// PVConv's BatchNorm3d + LeakyReLU applied to the conv output while the
+// devoxelization stages it, by the function the BatchNorm apply passes call
+// (bn_chan.hpp), so the activation is never written.
 
 // grid = (item splits, channel groups, b).  USE_LDS stages the block's
 // `cpb` rows (cpb * V floats) in LDS first.
 template <class Prov, bool USE_LDS>
 __global__ void __launch_bounds__(1024)
     gather_rows_kernel(const float* __restrict__ rows, float* __restrict__ out, int C, int V,
-                       int NI, int cpb, Prov prov, GatherEpi epi, RowBn bn) {
+                       int NI, int cpb, Prov prov, GatherEpi epi, BnParam bn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int T = Prov::TAPS;
   const int b = blockIdx.z;
@@ -234,7 +208,7 @@ __global__ void __launch_bounds__(1024)
     const int total = nc * V;
     if (bn.mean != nullptr) {  // block-uniform
       for (int e = threadIdx.x; e < total; e += blockDim.x)
-        lds[e] = row_bn_at(bn, c0 + e / V)(rb[e]);
+        lds[e] = bn.at(c0 + e / V).z(rb[e]);
     } else if ((((uintptr_t)rb) & 15) == 0 && (total & 3) == 0) {
       const float4* __restrict__ s4 = reinterpret_cast<const float4*>(rb);
       float4* d4 = reinterpret_cast<float4*>(lds);
@@ -269,13 +243,13 @@ __global__ void __launch_bounds__(1024)
           epi.add != nullptr ? epi.add + ((size_t)b * C + c0) * NI + i : nullptr;
       const float* __restrict__ sb = epi.scale != nullptr ? epi.scale + (size_t)b * C + c0 : nullptr;
       float ad[4], sc[4];
-      const bool abn = epi.add_mean != nullptr;  // block-uniform
+      const bool abn = epi.add_bn.mean != nullptr;  // block-uniform
       auto fetch = [&](int cq) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int cc = min(cq + k, nc - 1);
           ad[k] = ab != nullptr ? nt_ld(ab + (size_t)cc * NI) : 0.0f;
-          if (abn) ad[k] = add_bn_at(epi, c0 + cc)(ad[k]);
+          if (abn) ad[k] = add_bn_at(epi, c0 + cc).z(ad[k]);
           sc[k] = sb != nullptr ? sb[cc] : 1.0f;
         }
       };
@@ -312,7 +286,7 @@ __global__ void __launch_bounds__(1024)
 template <class Prov, int IPT>
 __global__ void __launch_bounds__(1024)
     gather_rows1_kernel(const float* __restrict__ rows, float* __restrict__ out, int C, int V,
-                        int NI, Prov prov, GatherEpi epi, RowBn bn) {
+                        int NI, Prov prov, GatherEpi epi, BnParam bn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int T = Prov::TAPS;
   const int b = blockIdx.z;
@@ -322,14 +296,14 @@ __global__ void __launch_bounds__(1024)
     const float4* __restrict__ s4 = reinterpret_cast<const float4*>(rb);
     float4* d4 = reinterpret_cast<float4*>(lds);
     if (bn.mean != nullptr) {  // block-uniform
-      const RowBnC f = row_bn_at(bn, c0);
-      for (int e = threadIdx.x; e < (V >> 2); e += blockDim.x) d4[e] = f(s4[e]);
+      const BnChan f = bn.at(c0);
+      for (int e = threadIdx.x; e < (V >> 2); e += blockDim.x) d4[e] = f.z(s4[e]);
     } else {
       for (int e = threadIdx.x; e < (V >> 2); e += blockDim.x) d4[e] = s4[e];
     }
   } else if (bn.mean != nullptr) {
-    const RowBnC f = row_bn_at(bn, c0);
-    for (int e = threadIdx.x; e < V; e += blockDim.x) lds[e] = f(rb[e]);
+    const BnChan f = bn.at(c0);
+    for (int e = threadIdx.x; e < V; e += blockDim.x) lds[e] = f.z(rb[e]);
   } else {
     for (int e = threadIdx.x; e < V; e += blockDim.x) lds[e] = rb[e];
   }
@@ -337,8 +311,8 @@ __global__ void __launch_bounds__(1024)
   float* __restrict__ ob = out + ((size_t)b * C + c0) * NI;
   const float* __restrict__ ab = epi.add != nullptr ? epi.add + ((size_t)b * C + c0) * NI : nullptr;
   const float sc = epi.scale != nullptr ? epi.scale[(size_t)b * C + c0] : 1.0f;
-  const bool abn = epi.add_mean != nullptr;  // block-uniform
-  const RowBnC fa = add_bn_at(epi, c0);
+  const bool abn = epi.add_bn.mean != nullptr;  // block-uniform
+  const BnChan fa = add_bn_at(epi, c0);
   const bool primary = blockIdx.y == 0;
   const int stride = gridDim.x * blockDim.x;
   for (int i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < NI; i0 += IPT * stride) {
@@ -358,7 +332,7 @@ __global__ void __launch_bounds__(1024)
       if (i < NI) {
         float acc = tap_sum<T>(lds, id[u], w[u]);
         if (epi.scale != nullptr) acc *= sc;
-        if (ab != nullptr) acc += abn ? fa(ad[u]) : ad[u];
+        if (ab != nullptr) acc += abn ? fa.z(ad[u]) : ad[u];
         ob[i] = acc;
       }
     }
@@ -400,7 +374,7 @@ __device__ __forceinline__ float4 tap_sum4(const float4* __restrict__ s, const i
 template <class Prov>
 __global__ void __launch_bounds__(512)
     gather_rows4_kernel(const float* __restrict__ rows, float* __restrict__ out, int C, int V,
-                        int NI, Prov prov, GatherEpi epi, RowBn bn) {
+                        int NI, Prov prov, GatherEpi epi, BnParam bn) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   float4* lds4 = reinterpret_cast<float4*>(lds);
   constexpr int T = Prov::TAPS;
@@ -408,11 +382,10 @@ __global__ void __launch_bounds__(512)
   const int c0 = blockIdx.y * 4;
   const float* __restrict__ rb = rows + ((size_t)b * C + c0) * V;
   if (bn.mean != nullptr) {  // block-uniform
-    const RowBnC f0 = row_bn_at(bn, c0), f1 = row_bn_at(bn, c0 + 1), f2 = row_bn_at(bn, c0 + 2),
-                 f3 = row_bn_at(bn, c0 + 3);
+    const BnChan f0 = bn.at(c0), f1 = bn.at(c0 + 1), f2 = bn.at(c0 + 2), f3 = bn.at(c0 + 3);
     for (int v = threadIdx.x; v < V; v += blockDim.x)
-      lds4[v] = make_float4(f0(rb[v]), f1(rb[(size_t)V + v]), f2(rb[2 * (size_t)V + v]),
-                            f3(rb[3 * (size_t)V + v]));
+      lds4[v] = make_float4(f0.z(rb[v]), f1.z(rb[(size_t)V + v]), f2.z(rb[2 * (size_t)V + v]),
+                            f3.z(rb[3 * (size_t)V + v]));
   } else {
     for (int v = threadIdx.x; v < V; v += blockDim.x)
       lds4[v] =
@@ -426,8 +399,8 @@ __global__ void __launch_bounds__(512)
 #pragma unroll
     for (int k = 0; k < 4; ++k) sc[k] = epi.scale[(size_t)b * C + c0 + k];
   }
-  const bool abn = epi.add_mean != nullptr;  // block-uniform
-  const RowBnC fa[4] = {add_bn_at(epi, c0), add_bn_at(epi, c0 + 1), add_bn_at(epi, c0 + 2),
+  const bool abn = epi.add_bn.mean != nullptr;  // block-uniform
+  const BnChan fa[4] = {add_bn_at(epi, c0), add_bn_at(epi, c0 + 1), add_bn_at(epi, c0 + 2),
                         add_bn_at(epi, c0 + 3)};
   const bool primary = blockIdx.y == 0;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < NI; i += gridDim.x * blockDim.x) {
@@ -445,7 +418,7 @@ __global__ void __launch_bounds__(512)
     for (int k = 0; k < 4; ++k) {
       float acc = r[k];
       if (epi.scale != nullptr) acc *= sc[k];
-      if (ab != nullptr) acc += abn ? fa[k](ad[k]) : ad[k];
+      if (ab != nullptr) acc += abn ? fa[k].z(ad[k]) : ad[k];
       ob[(size_t)k * NI + i] = acc;
     }
   }
@@ -530,7 +503,7 @@ inline bool prov_has_side_outputs(const ProvDevox& p) { return p.inds_out != nul
 template <class Prov>
 inline int launch_gather(const float* rows, float* out, int B, int C, int V, int NI, Prov prov,
                          hipStream_t st, const char* what, GatherEpi epi = GatherEpi{},
-                         RowBn bn = RowBn{}) {
+                         BnParam bn = BnParam{}) {
   if (B == 0 || NI == 0) return PCFM_OK;
   if (V == 0 && C > 0 && epi.add == nullptr) {  // empty rows: every tap is out of range -> zeros
     hipError_t e = hipMemsetAsync(out, 0, (size_t)B * C * NI * sizeof(float), st);

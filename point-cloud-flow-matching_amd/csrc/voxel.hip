@@ -97,13 +97,13 @@ __global__ void __launch_bounds__(256)
 // records {kind, b, c, i, got bits, want bits, lane, i / 64}.
 constexpr int kVerifyRecs = 16;
 // bn / abn (mean != nullptr): the grid rows / the add operand enter as
-// act(bn(.)) (pcfm_trilinear_devoxelize_bn_scale_add_fwd's RowBn transforms)
+// act(bn(.)) (pcfm_trilinear_devoxelize_bn_scale_add_fwd's BnParam transforms)
 __global__ void __launch_bounds__(256)
     devox_verify_kernel(const float* __restrict__ coords, const float* __restrict__ feat,
                         const float* __restrict__ scale, const float* __restrict__ add,
                         const float* __restrict__ out, const int* __restrict__ inds,
                         const float* __restrict__ wgts, int C, int n, int r, int* __restrict__ rec,
-                        RowBn bn = {}, RowBn abn = {}) {
+                        BnParam bn = {}, BnParam abn = {}) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const int b = blockIdx.y;
   if (t >= (long long)C * n) return;
@@ -116,17 +116,17 @@ __global__ void __launch_bounds__(256)
   const float* row = feat + ((size_t)b * C + c) * s;
   float a;
   if (bn.mean != nullptr) {  // tap_sum's order on the transformed values
-    const RowBnC tc = row_bn_at(bn, c);
-    a = w[1] * tc(row[id[1]]);
-    a = __builtin_fmaf(w[0], tc(row[id[0]]), a);
-    for (int k = 2; k < 8; ++k) a = __builtin_fmaf(w[k], tc(row[id[k]]), a);
+    const BnChan tc = bn.at(c);
+    a = w[1] * tc.z(row[id[1]]);
+    a = __builtin_fmaf(w[0], tc.z(row[id[0]]), a);
+    for (int k = 2; k < 8; ++k) a = __builtin_fmaf(w[k], tc.z(row[id[k]]), a);
   } else {
     a = tap_sum<8>(row, id, w);
   }
   if (scale != nullptr) a *= scale[(size_t)b * C + c];
   if (add != nullptr) {
     const float av = add[((size_t)b * C + c) * n + i];
-    a += abn.mean != nullptr ? row_bn_at(abn, c)(av) : av;
+    a += abn.mean != nullptr ? abn.at(c).z(av) : av;
   }
   const float got = out[((size_t)b * C + c) * n + i];
   auto note = [&](int kind, float gv, float wv) {
@@ -191,8 +191,8 @@ extern "C" int pcfm_debug_devox_verify_bn(const float* coords, const float* feat
                                          add_gamma != nullptr && add_beta != nullptr),
                  "debug_devox_verify_bn: incomplete BatchNorm operands of add");
   if ((long long)b * c * n == 0) return PCFM_OK;
-  const RowBn bn{bn_mean, bn_invstd, bn_gamma, bn_beta, slope};
-  const RowBn abn{add_mean, add_invstd, add_gamma, add_beta, add_slope};
+  const BnParam bn{bn_mean, bn_invstd, bn_gamma, bn_beta, slope};
+  const BnParam abn{add_mean, add_invstd, add_gamma, add_beta, add_slope};
   hipLaunchKernelGGL(devox_verify_kernel, dim3(ceil_div((long long)c * n, 256), b), dim3(256), 0,
                      (hipStream_t)stream, coords, feat, scale, add, out, inds, wgts, c, n, r, rec,
                      bn, abn);
@@ -311,7 +311,7 @@ extern "C" int pcfm_trilinear_devoxelize_scale_add_fwd(const float* coords, cons
 
 // scale[b, c] * devox(act(bn(x)))[b, c, i] + add'[b, c, i]: PVConv's second
 // BatchNorm3d + LeakyReLU applied to the conv output x as the gather stages its
-// rows (rows.hpp RowBn), so the activation is never written (norm.hip,
+// rows (bn_chan.hpp BnChan::z), so the activation is never written (norm.hip,
 // pcfm_bn_act_fwd_rowmean); add' = add, or act(bn(add)) with its own BatchNorm
 // operands (the point branch's BatchNorm1d + ReLU, SharedMLP's activation
 // never written either).
@@ -337,17 +337,8 @@ extern "C" int pcfm_trilinear_devoxelize_bn_scale_add_fwd(
   GatherEpi epi;
   epi.scale = scale;
   epi.add = add;
-  epi.add_mean = add_mean;
-  epi.add_invstd = add_invstd;
-  epi.add_gamma = add_gamma;
-  epi.add_beta = add_beta;
-  epi.add_slope = add_slope;
-  RowBn bn;
-  bn.mean = bn_mean;
-  bn.invstd = bn_invstd;
-  bn.gamma = gamma;
-  bn.beta = beta;
-  bn.slope = slope;
+  epi.add_bn = BnParam{add_mean, add_invstd, add_gamma, add_beta, add_slope};
+  const BnParam bn{bn_mean, bn_invstd, gamma, beta, slope};
   return launch_gather(x, out, b, c, s, n, prov, (hipStream_t)stream,
                        "trilinear_devoxelize_bn_scale_add_fwd", epi, bn);
 }

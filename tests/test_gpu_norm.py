@@ -20,7 +20,13 @@ def ops():
 @pytest.mark.parametrize("shape,slope,eps", [((8, 256, 20000), 0.0, 1e-5),
                                              ((2, 128, 16, 16, 16), 0.1, 1e-4),
                                              ((3, 64, 100), 0.0, 1e-5),
-                                             ((1, 32, 8, 8, 8), 0.1, 1e-4)])
+                                             ((1, 32, 8, 8, 8), 0.1, 1e-4),
+                                             # 18 statistics parts, 6 per row of 9 float4s: the
+                                             # last part empty; C % 4 != 0 in the bias finalize
+                                             ((3, 5, 36), 0.0, 1e-5),
+                                             # 16 parts of 1094 float4s: the smallest row whose
+                                             # strips enter the prefetch loop and then its tail
+                                             ((1, 4, 70000), 0.1, 1e-4)])
 def test_bn_act_matches_torch(ops, shape, slope, eps):
     from modules.norm_act import bn_act, _fusable
     torch.manual_seed(0)
@@ -64,6 +70,36 @@ def test_bn_act_falls_back_in_eval(ops):
     x = torch.randn(2, 16, 40, device="cuda")
     assert not _fusable(x, bn)
     torch.testing.assert_close(bn_act(x, bn, 0.0), torch.relu(bn(x)))
+
+
+@pytest.mark.parametrize("shape", [(3, 5, 36), (1, 4, 70000), (2, 64, 4, 4, 4)])
+def test_bn_forward_statistics_agree_across_entries(ops, shape):
+    """The statistics-only entry (paired with the gather-side BatchNorm by
+    modules/pvconv.py and norm_act.py) and the two fused forward entries run the
+    same statistics pass and the same finalize: mean, invstd, the running pair
+    and the counter are bit-equal."""
+    g = torch.Generator(device="cuda").manual_seed(11)
+    c = shape[1]
+    x = torch.randn(*shape, device="cuda", generator=g) * 2.0 + 3.0
+    gamma = torch.rand(c, device="cuda", generator=g) + 0.5
+    beta = torch.rand(c, device="cuda", generator=g) - 0.5
+    rm0 = torch.rand(c, device="cuda", generator=g) - 0.5
+    rv0 = torch.rand(c, device="cuda", generator=g) + 0.5
+    got = []
+    for entry in ("stats", "act", "rowmean"):
+        rm, rv = rm0.clone(), rv0.clone()
+        nbt = torch.full((), 3, dtype=torch.int64, device="cuda")
+        if entry == "stats":
+            m, iv = ops.bn_forward_stats(x, 1e-5, 0.1, rm, rv, nbt)
+        elif entry == "act":
+            _, m, iv = ops.bn_act_forward(x, gamma, beta, 1e-5, 0.1, 0.1, rm, rv, nbt)
+        else:
+            _, m, iv = ops.bn_act_forward_rowmean(x, gamma, beta, 1e-5, 0.1, 0.1, rm, rv, nbt)
+        got.append((m.clone(), iv.clone(), rm, rv, nbt))
+    assert int(got[0][4]) == 4 and not torch.equal(got[0][2], rm0)
+    for other in got[1:]:
+        for a, e in zip(other, got[0]):
+            assert torch.equal(a, e)
 
 
 @pytest.mark.parametrize("b,c,n,groups", [(8, 256, 20000, 32), (2, 128, 1000, 32), (3, 64, 36, 8)])
