@@ -320,186 +320,25 @@ __global__ void __launch_bounds__(256)
 }
 
 // ---------------------------------------------------------------------------
-// Forward / backward-data implicit GEMM over the channels-last split input.
-// grid = (V / TN) * (M / TM) * B (1-D); K-steps s = tap * (K / KT) + channel chunk.
-// A = pre-split weights W'[tap][m][k], B = pre-split input rows xs[b][v][k]:
-// every staging access is a 16-B copy (no per-tap split arithmetic).  KT = 64
-// channels per step: 48 MFMAs per wave between barriers (TM = TN = 128).
-// LDS rows are KT + 8 bf16 (144 B): conflict-free ds_read_b128 fragments.
+// Forward / backward-data implicit GEMM over the channels-last split input:
+// A = pre-split weights W'[tap][m][k], B = pre-split input rows xs[b][v][k];
+// K-steps s = (channel chunk, tap), chunk-major.  Three kernels below -- the
+// LDS-DMA, window and slab forms -- that differ only in where a step's B
+// fragments come from; the blocks they share come first (the LDS-DMA kernel
+// keeps its own copies of some, see there).
+//
+// (Removed: the register-staged tile kernel conv3_igemm_cl_kernel -- 128 x 128
+// or split-K 64 x 64 tiles, KT = 64 channels per step, 48 MFMAs per wave
+// between two barriers, 144-B LDS rows -- the first form written and the
+// fall-back where the LDS-DMA kernel did not apply.  No supported shape reaches
+// it: conv3_shape_ok demands r^3 % 128 == 0, i.e. 3 v2(r) >= 7, so 8 | r and
+// r^3 % 512 == 0 -- the LDS-DMA kernel's V % 256 == 0 and V >= 512 -- and
+// cout % 128 == 0, its M tile; cin % 64 == 0 gives whole, and an even number
+// of, 32-channel K-steps.  For the same reason the KT = 16 instantiation of
+// the LDS-DMA kernel, kept for cin % 32 != 0, could not run: 32-B rows, two
+// blocks per CU, measured 1.15-1.18x slower where forced.  The build switches
+// that forced either, or sent r = 8 to the 64 x 64 tiles, went with them.)
 // ---------------------------------------------------------------------------
-template <int TM, int TN, int KT>
-struct TileK {
-  static constexpr int LDR = KT + 8;
-  static constexpr int SI = TM / 64, SJ = TN / 64;
-  static constexpr int A_ELEMS = TM * LDR, B_ELEMS = TN * LDR;
-  static constexpr int BUF = 2 * A_ELEMS + 2 * B_ELEMS;
-  static constexpr int CPR = KT / 8;               // 16-B chunks per row
-  static constexpr int QA = TM * CPR / 256;        // A chunks per thread (per image)
-  static constexpr int QB = TN * CPR / 256;        // B chunks per thread (per image)
-};
-
-template <int TM, int TN, int KT>
-__device__ __forceinline__ void tile_mfma_k(const uint16_t* buf, int wr, int wc, int r, int h,
-                                            f32x16 (&acc)[TM / 64][TN / 64]) {
-  using T = TileK<TM, TN, KT>;
-  const uint16_t* sAh = buf;
-  const uint16_t* sAl = buf + T::A_ELEMS;
-  const uint16_t* sBh = buf + 2 * T::A_ELEMS;
-  const uint16_t* sBl = sBh + T::B_ELEMS;
-#pragma unroll
-  for (int kk = 0; kk < KT / 16; ++kk) {
-    bf16x8 ah[T::SI], al[T::SI], bh[T::SJ], bl[T::SJ];
-#pragma unroll
-    for (int i = 0; i < T::SI; ++i) {
-      const int o = (wr * (TM / 2) + i * 32 + r) * T::LDR + kk * 16 + 8 * h;
-      ah[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sAh + o));
-      al[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sAl + o));
-    }
-#pragma unroll
-    for (int j = 0; j < T::SJ; ++j) {
-      const int o = (wc * (TN / 2) + j * 32 + r) * T::LDR + kk * 16 + 8 * h;
-      bh[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sBh + o));
-      bl[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sBl + o));
-    }
-    // product-major order: consecutive MFMAs write different accumulators
-#pragma unroll
-    for (int i = 0; i < T::SI; ++i)
-#pragma unroll
-      for (int j = 0; j < T::SJ; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < T::SI; ++i)
-#pragma unroll
-      for (int j = 0; j < T::SJ; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < T::SI; ++i)
-#pragma unroll
-      for (int j = 0; j < T::SJ; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-  }
-}
-
-template <int TM, int TN, int KT>
-__global__ void __launch_bounds__(256)
-    conv3_igemm_cl_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl,
-                          const uint16_t* __restrict__ wh, const uint16_t* __restrict__ wl,
-                          const float* __restrict__ bias, float* __restrict__ y, int K, int M,
-                          int R, int S, float* __restrict__ part) {
-  using T = TileK<TM, TN, KT>;
-  __shared__ __attribute__((aligned(16))) uint16_t lds[T::BUF];
-  const int V = R * R * R, R2 = R * R;
-  // 1-D grid of (m tile, voxel tile, b) items, m fastest, dealt to the 8 XCDs
-  // in contiguous runs (T1 remap): an XCD sweeps a contiguous slab of the grid,
-  // so the 27 taps' neighbour rows of concurrently resident blocks overlap in
-  // its L2 instead of streaming from the Infinity Cache.
-  int id = (int)blockIdx.x;
-  {
-    const int nwg = (int)gridDim.x, q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-    id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-  }
-  const int nmt = M / TM, nvt = V / TN;
-  const int items = (int)gridDim.x / S;  // split-K: S K-ranges per output tile, split outermost
-  const int sp = id / items;
-  id -= sp * items;
-  const int m0 = (id % nmt) * TM;
-  id /= nmt;
-  const int v0 = (id % nvt) * TN, b = id / nvt;
-  const int t = threadIdx.x, lane = t & 63;
-  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int wr = w >> 1, wc = w & 1, r = lane & 31, h = lane >> 5;
-  const uint16_t* __restrict__ xbh = xh + (size_t)b * V * 2 * K;
-  const uint16_t* __restrict__ xbl = xl + (size_t)b * V * 2 * K;
-  const int nck = K / KT, nall = 27 * nck;
-  const int s0 = (int)((long long)nall * sp / S), nsteps = (int)((long long)nall * (sp + 1) / S) - s0;
-  // chunk q of this thread: row (t + 256 q) / CPR, 8-channel column (t % CPR) * 8
-  const int col = (t % T::CPR) * 8;
-  int bv[T::QB], bx[T::QB], by[T::QB], bz[T::QB];
-#pragma unroll
-  for (int q = 0; q < T::QB; ++q) {
-    bv[q] = v0 + (t + 256 * q) / T::CPR;
-    bx[q] = bv[q] / R2;
-    by[q] = (bv[q] / R) % R;
-    bz[q] = bv[q] % R;
-  }
-
-  StageVec<T::QA> rah, ral;
-  StageVec<T::QB> rbh, rbl;
-  auto load = [&](int s) {
-    const int c0 = (s / 27) * KT, tap = s - (s / 27) * 27;  // chunk-major (L2 reuse)
-#pragma unroll
-    for (int q = 0; q < T::QA; ++q) {
-      const int row = (t + 256 * q) / T::CPR;
-      const size_t g = split_off((size_t)tap * M + m0 + row, c0 + col, K);
-      sv_put<T::QA>(rah, q, *reinterpret_cast<const uint4*>(wh + g));
-      sv_put<T::QA>(ral, q, *reinterpret_cast<const uint4*>(wl + g));
-    }
-    const int dx = tap / 9 - 1, dy = (tap / 3) % 3 - 1, dz = tap % 3 - 1;
-    const int doff = dx * R2 + dy * R + dz;
-#pragma unroll
-    for (int q = 0; q < T::QB; ++q) {
-      const bool inb = (unsigned)(bx[q] + dx) < (unsigned)R &&
-                       (unsigned)(by[q] + dy) < (unsigned)R && (unsigned)(bz[q] + dz) < (unsigned)R;
-      const size_t o = split_off((size_t)(inb ? bv[q] + doff : bv[q]), c0 + col, K);
-      const uint4 hv = *reinterpret_cast<const uint4*>(xbh + o);
-      const uint4 lv = *reinterpret_cast<const uint4*>(xbl + o);
-      sv_put<T::QB>(rbh, q, inb ? hv : uint4{0u, 0u, 0u, 0u});
-      sv_put<T::QB>(rbl, q, inb ? lv : uint4{0u, 0u, 0u, 0u});
-    }
-  };
-  auto store = [&](uint16_t* buf) {
-#pragma unroll
-    for (int q = 0; q < T::QA; ++q) {
-      uint16_t* d = buf + ((t + 256 * q) / T::CPR) * T::LDR + col;
-      *reinterpret_cast<uint4*>(d) = sv_get<T::QA>(rah, q);
-      *reinterpret_cast<uint4*>(d + T::A_ELEMS) = sv_get<T::QA>(ral, q);
-    }
-#pragma unroll
-    for (int q = 0; q < T::QB; ++q) {
-      uint16_t* d = buf + 2 * T::A_ELEMS + ((t + 256 * q) / T::CPR) * T::LDR + col;
-      *reinterpret_cast<uint4*>(d) = sv_get<T::QB>(rbh, q);
-      *reinterpret_cast<uint4*>(d + T::B_ELEMS) = sv_get<T::QB>(rbl, q);
-    }
-  };
-
-  f32x16 acc[T::SI][T::SJ];
-#pragma unroll
-  for (int i = 0; i < T::SI; ++i)
-#pragma unroll
-    for (int j = 0; j < T::SJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-
-  load(s0);
-  store(lds);
-  __syncthreads();
-  for (int s = 0; s < nsteps; ++s) {
-    if (s + 1 < nsteps) load(s0 + s + 1);
-    tile_mfma_k<TM, TN, KT>(lds, wr, wc, r, h, acc);
-    __syncthreads();
-    if (s + 1 < nsteps) store(lds);
-    __syncthreads();
-  }
-  // S == 1: y (+ bias); else this split's partial, summed in split order by
-  // conv3_ksum_kernel (deterministic)
-  const int nb = items / (nmt * nvt);  // batch elements
-  float* __restrict__ yb =
-      S == 1 ? y + (size_t)b * M * V : part + ((size_t)sp * nb + b) * M * V;
-  float biasv[T::SI][16];
-#pragma unroll
-  for (int i = 0; i < T::SI; ++i)
-    load_bias16(S == 1 ? bias : nullptr, m0 + wr * (TM / 2) + i * 32, h, M, biasv[i]);
-#pragma unroll
-  for (int i = 0; i < T::SI; ++i)
-#pragma unroll
-    for (int j = 0; j < T::SJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wr * (TM / 2) + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        const int v = v0 + wc * (TN / 2) + j * 32 + r;
-        yb[(size_t)m * V + v] = acc[i][j][e] + biasv[i][e];
-      }
-}
 
 // y[b][m][v] = bias[m] + sum_sp part[sp][b][m][v], float4 per thread
 __global__ void __launch_bounds__(256)
@@ -540,12 +379,13 @@ __global__ void __launch_bounds__(256)
 // ---------------------------------------------------------------------------
 constexpr int kGM = 128, kGN = 256, kGStages = 3;
 
-// K-step geometry of the LDS-DMA kernel: KT = 32 (64-B rows, 48 KiB stages,
-// one block per CU) or KT = 16 (32-B rows, 24 KiB stages, two blocks per CU)
+// K-step geometry of the three forms: 32 channels per step, i.e. 64-B LDS rows
+// (hi or lo) moved as 1-KiB LDS-DMA pieces of 16 rows.
 // GN: voxels per block tile (256: 8 waves, one block per CU; 128: 4 waves and
 // two stages, two independent blocks per CU)
-template <int KT, int GN = kGN>
+template <int GN = kGN>
 struct GK {
+  static constexpr int KT = 32;
   static constexpr int NW = 2 * (GN / 64);     // waves: 2 (m) x GN / 64 (voxels)
   static constexpr int RB = KT * 2;            // bytes per LDS row (hi or lo)
   static constexpr int CPR = RB / 16;          // 16-B chunks per row
@@ -556,9 +396,7 @@ struct GK {
   static constexpr int API = A / 1024, BPI = B / 1024;                  // pieces per image
   // physical chunk p of row r holds logical chunk p ^ swz(r): conflict-free
   // ds_read_b128 fragment reads
-  static __device__ __forceinline__ int swz(int row) {
-    return KT == 32 ? (row >> 2) & 3 : (row >> 3) & 1;
-  }
+  static __device__ __forceinline__ int swz(int row) { return (row >> 2) & 3; }
 };
 
 __device__ __forceinline__ void glds16(const void* g, uint8_t* l) {
@@ -566,15 +404,173 @@ __device__ __forceinline__ void glds16(const void* g, uint8_t* l) {
                                    (void __attribute__((address_space(3)))*)l, 16, 0, 0);
 }
 
-// One step's MFMA operands of a wave (64 x 64 of the 128 x 256 tile):
-// F[kk] = {A hi 0, A hi 1, A lo 0, A lo 1, B hi 0, B hi 1, B lo 0, B lo 1}
-template <int KT, int GN = kGN>
+// LDS-DMA as inline asm: hipcc does not see it, so it inserts no vmcnt(0)
+// before the step's LDS reads (it does for __builtin_amdgcn_global_load_lds
+// here, which serialises the prefetch with the compute); completion is waited
+// for by hand.  M0 is set and restored inside the statement.
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+__device__ __forceinline__ void glds16_asm(const void* g, uint32_t lds) {
+  unsigned keep;
+  asm volatile(
+      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
+      "s_mov_b32 m0, %0"
+      : "=&s"(keep)
+      : "v"(g), "s"(lds)
+      : "memory");
+}
+
+// voxel offset of tap = 9 (dx + 1) + 3 (dy + 1) + dz + 1
+// (R2 = R * R from the caller, computed once: written as dx * R * R here the
+// compiler turns the sum into (dx R + dy) R + dz and the LDS-DMA kernel's
+// per-step row offset into a 64 x 64-bit multiply)
+__device__ __forceinline__ int tap_delta(int tap, int R2, int R) {
+  return (tap / 9 - 1) * R2 + ((tap / 3) % 3 - 1) * R + (tap % 3 - 1);
+}
+
+// a channel chunk's place in an interleaved row (split_off; a 32-channel chunk
+// never straddles a group)
+__device__ __forceinline__ int split_cof(int c0) { return ((c0 >> 5) << 6) + (c0 & 31); }
+
+// bit t: tap t's neighbour of voxel v is inside the volume.  Built once per
+// row, so a step tests a bit instead of three ranges (which hipcc compiled to
+// exec-mask branches per piece)
+__device__ __forceinline__ uint32_t tap_valid27(int v, int R) {
+  const int R2 = R * R;
+  const int x = v / R2, yy = (v / R) % R, z = v % R;
+  // per axis: bit (d + 1) set when coordinate + d is inside [0, R)
+  const uint32_t ax = (x > 0 ? 1u : 0u) | 2u | (x + 1 < R ? 4u : 0u);
+  const uint32_t ay = (yy > 0 ? 1u : 0u) | 2u | (yy + 1 < R ? 4u : 0u);
+  const uint32_t az = (z > 0 ? 1u : 0u) | 2u | (z + 1 < R ? 4u : 0u);
+  uint32_t m = 0u;
+#pragma unroll
+  for (int t = 0; t < 27; ++t)
+    m |= (((ax >> (t / 9)) & (ay >> ((t / 3) % 3)) & (az >> (t % 3))) & 1u) << t;
+  return m;
+}
+
+// The weight (A) operand of a block's K-steps, the same in all three forms: a
+// step's 128 rows x 32 channels (hi | lo image, 16 pieces) are dealt APW per
+// wave, piece I = APW w + q -> image I / API, rows (I % API) * RPP + lane / CPR.
+// The lane's part of the source address is fixed (weight_bases); a step adds
+// the uniform (tap, chunk) offset (issue_weights).  `put(src, image, piece)` is
+// the form's issue primitive to byte image * G::A + piece * 1024 of its stage:
+// glds16, or glds16_asm where the compiler must not see the DMA (the two
+// differ on purpose, see glds16_asm).
+template <class G>
+__device__ __forceinline__ void weight_bases(const uint16_t* wh, const uint16_t* wl, int m0, int K,
+                                             int w, int lane, const uint16_t* (&base)[G::APW]) {
+  const int prow = lane / G::CPR, pch = lane % G::CPR;
+#pragma unroll
+  for (int q = 0; q < G::APW; ++q) {
+    const int I = G::APW * w + q;
+    const int row = (I % G::API) * G::RPP + prow;
+    base[q] = ((I / G::API) ? wl : wh) + (size_t)(m0 + row) * 2 * K + ((pch ^ G::swz(row)) << 3);
+  }
+}
+template <class G, class Put>
+__device__ __forceinline__ void issue_weights(const uint16_t* const (&base)[G::APW], int tap, int c0,
+                                              int M, int K, int w, Put&& put) {
+  const size_t aofs = (size_t)tap * M * 2 * K + split_cof(c0);
+#pragma unroll
+  for (int q = 0; q < G::APW; ++q) {
+    const int I = G::APW * w + q;
+    put(base[q] + aofs, I / G::API, I % G::API);
+  }
+}
+
+// The hi and lo fragment (k-chunk kc = 2 kk + h) of row `row` of a swizzled
+// image pair: hi at `img`, lo `lo` bytes behind it
+template <class G>
+__device__ __forceinline__ void frag_hl(const uint8_t* img, int lo, int row, int kc, bf16x8& fh,
+                                        bf16x8& fl) {
+  const int off = row * G::RB + ((kc ^ G::swz(row)) << 4);
+  fh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(img + off));
+  fl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(img + lo + off));
+}
+
+// a fragment's 8 K-elements ANDed with masks for elements 0-1, 2-5 and 6-7
+__device__ __forceinline__ bf16x8 mask_k8(bf16x8 v, uint32_t m0, uint32_t m12, uint32_t m3) {
+  uint4 u = __builtin_bit_cast(uint4, v);
+  u.x &= m0;
+  u.y &= m12;
+  u.z &= m12;
+  u.w &= m3;
+  return __builtin_bit_cast(bf16x8, u);
+}
+
+// One step's MFMA operands of a wave (64 x 64 of the tile): two 16-deep
+// K-slices of two A row blocks (i) and two B column blocks (j), hi and lo
+struct FragK {
+  bf16x8 ah[2], al[2], bh[2], bl[2];
+};
+using Frags = FragK[2];
+
+// A from rows arow + 32 i of the weight stage `a` (hi | lo), B from rows
+// brow[j] of the image pair at `b` (lo `blo` bytes behind hi)
+template <class G>
+__device__ __forceinline__ void read_frags(const uint8_t* a, int arow, const uint8_t* b, int blo,
+                                           const int (&brow)[2], int h, Frags& F) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      frag_hl<G>(a, G::A, arow + i * 32, 2 * kk + h, F[kk].ah[i], F[kk].al[i]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) frag_hl<G>(b, blo, brow[j], 2 * kk + h, F[kk].bh[j], F[kk].bl[j]);
+  }
+}
+
+__device__ __forceinline__ void frags_mfma(const Frags& F, f32x16 (&acc)[2][2]) {
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) mfma_x3(F[kk].ah, F[kk].al, F[kk].bh, F[kk].bl, acc);
+}
+
+// Epilogue of a wave's 64 x 64 tile: rows mg + 32 i + (accumulator row), this
+// lane's two dense output columns col(j) (element (m, column) at col(j) + m V);
+// + bias, streamed stores (cached stores: same-box bench 33.57 -> 33.70 ms/step)
+template <class Col>
+__device__ __forceinline__ void tile_epilogue(const f32x16 (&acc)[2][2],
+                                              const float* __restrict__ bias, int mg, int h, int M,
+                                              int V, Col&& col) {
+  float biasv[2][16];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) load_bias16(bias, mg + i * 32, h, M, biasv[i]);
+  float* ycol[2] = {col(0), col(1)};
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int m = mg + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        nt_st(acc[i][j][e] + biasv[i][e], ycol[j] + (size_t)m * V);
+      }
+}
+
+// ---------------------------------------------------------------------------
+// LDS-DMA form: every step DMAs the weight slice and the tile's GN input rows
+// shifted by its tap into one of NST stages.
+//
+// This kernel is kept instruction for instruction (tools/isa_same.py,
+// profiles/conv_core_isa.json): written on the blocks above -- tap_valid27,
+// weight_bases / issue_weights, read_frags / frags_mfma, zero_acc,
+// tile_epilogue with a nullable column -- its K loop came out with the same
+// instructions in another order and the masked launches at C128 R32 / C256 R16
+// measured 0.6-2.9 % slower than the parent's own spread of 0.3 %
+// (tools/conv_ab.py, MI355X; each block alone changes the code object, only
+// xcd_deal does not).  So its A pieces, its tap mask, its fragment reads
+// (glds_frags / glds_mfma: the [8]-array form of read_frags / frags_mfma), its
+// accumulator zeroing and its dense-or-listed epilogue stay written out here.
+// ---------------------------------------------------------------------------
+template <int GN>
 __device__ __forceinline__ void glds_frags(const uint8_t* lds, int buf, int wr, int wc, int r,
-                                           int h, bf16x8 (&F)[KT / 16][8]) {
-  using G = GK<KT, GN>;
+                                           int h, bf16x8 (&F)[2][8]) {
+  using G = GK<GN>;
   const uint8_t* base = lds + buf * G::STAGE;
 #pragma unroll
-  for (int kk = 0; kk < KT / 16; ++kk) {
+  for (int kk = 0; kk < 2; ++kk) {
     const int kc = 2 * kk + h;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -592,11 +588,9 @@ __device__ __forceinline__ void glds_frags(const uint8_t* lds, int buf, int wr, 
     }
   }
 }
-
-template <int KT>
-__device__ __forceinline__ void glds_mfma(const bf16x8 (&F)[KT / 16][8], f32x16 (&acc)[2][2]) {
+__device__ __forceinline__ void glds_mfma(const bf16x8 (&F)[2][8], f32x16 (&acc)[2][2]) {
 #pragma unroll
-  for (int kk = 0; kk < KT / 16; ++kk) {
+  for (int kk = 0; kk < 2; ++kk) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -614,9 +608,8 @@ __device__ __forceinline__ void glds_mfma(const bf16x8 (&F)[KT / 16][8], f32x16 
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(F[kk][2 + i], F[kk][4 + j], acc[i][j], 0, 0, 0);
   }
 }
-
-template <int KT, int GN = kGN, int NST = kGStages>
-__global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
+template <int GN = kGN, int NST = kGStages>
+__global__ void __launch_bounds__(GN * 2)  // GK<GN>::NW = GN / 32 waves
     conv3_igemm_glds_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ xl,
                             const uint16_t* __restrict__ wh, const uint16_t* __restrict__ wl,
                             const uint16_t* __restrict__ zrow, const float* __restrict__ bias,
@@ -625,7 +618,8 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
                             int mmode, const int* __restrict__ vlist = nullptr,
                             const int* __restrict__ vcount = nullptr, int lg = 5,
                             const uint32_t* __restrict__ obits = nullptr) {
-  using G = GK<KT, GN>;
+  using G = GK<GN>;
+  constexpr int KT = G::KT;
   __shared__ __attribute__((aligned(16))) uint8_t lds[NST * G::STAGE];
   const int V = R * R * R, R2 = R * R;
   const int nmt = M / kGM, nvt = V / GN;
@@ -646,10 +640,9 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
     nwg = nmt * ((lcount + CPT - 1) / CPT);
     if (id >= nwg) return;
   }
-  {
-    const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-    id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-  }
+  // (m tile, voxel tile, b, split) items, m fastest: an XCD's contiguous run of
+  // them shares the 27 taps' neighbour rows in its L2
+  id = xcd_deal(id, nwg);
   const int nb = (int)gridDim.x / (S * nmt * nvt);  // batch elements
   const int m0 = (id % nmt) * kGM;
   id /= nmt;
@@ -688,8 +681,8 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
   const size_t bV = (size_t)b * V;
   const int prow = lane / G::CPR, pch = lane % G::CPR;  // this lane's place in a piece
 
-  // A pieces: I = APW w + q -> image I / API, rows (I % API) * RPP + lane / CPR.
-  // Per-piece element offsets are fixed; a step adds the uniform tap / chunk offset.
+  // A pieces (weight_bases, written out): I = APW w + q -> image I / API, rows
+  // (I % API) * RPP + lane / CPR
   const uint16_t* abase[G::APW];
 #pragma unroll
   for (int q = 0; q < G::APW; ++q) {
@@ -700,9 +693,8 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
   // B pieces: I = BPW w + q -> image I / BPI (waves 0-3: hi, 4-7: lo)
   const uint16_t* bbase[G::BPW];
   const uint16_t* zbase[G::BPW];
-  // bit t: tap t's neighbour of the piece's voxel is inside the volume (all 0 for
-  // padding).  Built once, so a step selects its source with a bit test instead
-  // of three range checks (which hipcc compiled to exec-mask branches per piece)
+  // tap_valid27 of the piece's voxel (all 0 for padding): a step selects its
+  // source row with a bit test
   uint32_t bval[G::BPW];
 #pragma unroll
   for (int q = 0; q < G::BPW; ++q) {
@@ -718,7 +710,6 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
     bbase[q] = ((I / G::BPI) ? xl : xh) + (size_t)(gv >= 0 ? gv : 0) * 2 * K + cofs;
     zbase[q] = zrow + cofs;
     const int x = v / R2, yy = (v / R) % R, z = v % R;
-    // per axis: bit (d + 1) set when coordinate + d is inside [0, R)
     const uint32_t ax = (x > 0 ? 1u : 0u) | 2u | (x + 1 < R ? 4u : 0u);
     const uint32_t ay = (yy > 0 ? 1u : 0u) | 2u | (yy + 1 < R ? 4u : 0u);
     const uint32_t az = (z > 0 ? 1u : 0u) | 2u | (z + 1 < R ? 4u : 0u);
@@ -733,6 +724,7 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
       uint32_t keep = 0u;
 #pragma unroll
       for (int t = 0; t < 27; ++t) {
+        // (term by term in 64 bits: summing tap_delta first costs scalar registers)
         const long long gn = gv + (t / 9 - 1) * R2 + ((t / 3) % 3 - 1) * R + (t % 3 - 1);
         const uint32_t word = ((m >> t) & 1u) ? obits[gn >> 5] : 0u;
         keep |= ((word >> (gn & 31)) & 1u) << t;
@@ -754,23 +746,16 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
       iseq = sl;
     }
     const int c0 = ichunk * KT, tap = itap;
-    // the chunk's place in an interleaved row (split_off; a KT-chunk never
-    // straddles a 32-channel group)
-    const int cof = ((c0 >> 5) << 6) + (c0 & 31);
     uint8_t* base = lds + buf * G::STAGE;
+    const int cof = split_cof(c0);
     const size_t aofs = (size_t)tap * M * 2 * K + cof;
-#ifndef PCFM_EXP_CNOA
 #pragma unroll
     for (int q = 0; q < G::APW; ++q) {
       const int I = G::APW * w + q;
       glds16(abase[q] + aofs, base + (I / G::API) * G::A + (I % G::API) * 1024);
     }
-#endif
     const int dx = tap / 9 - 1, dy = (tap / 3) % 3 - 1, dz = tap % 3 - 1;
     const long long bofs = (long long)(dx * R2 + dy * R + dz) * 2 * K + cof;
-#ifdef PCFM_EXP_CNOB
-    if (aofs == (size_t)-1)
-#endif
 #pragma unroll
     for (int q = 0; q < G::BPW; ++q) {
       const int I = G::BPW * w + q;
@@ -786,6 +771,9 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
     }
   };
 
+  // a step's fragments: A and the tile's 256 (GN) shifted B rows from stage buf
+  auto frags = [&](int buf, bf16x8 (&F)[2][8]) { glds_frags<GN>(lds, buf, wr, wc, r, h, F); };
+
   f32x16 acc[2][2];
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -795,23 +783,24 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
 
   if (nsteps > 0) {  // an all-skipped tile writes bias (forward) / 0 (backward-data)
-#ifndef PCFM_CONV_GLDS_NOPF
   // Fragment registers double-buffered across steps: after the barrier of
   // step s the waves read step s+1's fragments while step s's 24 MFMAs run,
   // so the LDS read latency of a step hides behind the previous step's
   // matrix work (the single-buffered form exposed it at every step: 2 waves
   // per SIMD cannot cover it).  Stage s's LDS buffer is refilled (stage s+3)
   // once every wave holds its fragments: lgkmcnt(0) + barrier.
-  bf16x8 F0[KT / 16][8], F1[KT / 16][8];
+  // (Measured and removed: that single-buffered loop, and a burst issue of
+  // step s + 3's pieces right after the barrier -- numbers below.)
+  bf16x8 F0[2][8], F1[2][8];
   issue(0, 0);
   if (nsteps > 1) issue(1, 1);
   if (nsteps > 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::APW + G::BPW) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   if (NST == 3 && nsteps > 2) issue(2, 2);
-  glds_frags<KT, GN>(lds, 0, wr, wc, r, h, F0);
+  frags(0, F0);
   // step s with the prefetch of step s+1 (s + 1 < nsteps)
-  auto step = [&](int s, bf16x8 (&Fc)[KT / 16][8], bf16x8 (&Fn)[KT / 16][8]) {
+  auto step = [&](int s, bf16x8 (&Fc)[2][8], bf16x8 (&Fn)[2][8]) {
     // stage s+1 landed (own pieces; with three stages, stage s+2's stay in flight)
     if (NST == 3 && s + 2 < nsteps)
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::APW + G::BPW) : "memory");
@@ -819,28 +808,18 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): this wave's stage-s reads done
     __builtin_amdgcn_s_barrier();
-#ifndef PCFM_CONV_DMA_LATE
-#define PCFM_CONV_DMA_LATE 4  // MFMAs per LDS-DMA piece; 0: the burst after the barrier
-#endif
-#if PCFM_CONV_DMA_LATE > 0
     // LDS-DMA issue (~60-185 cycles per piece) between the MFMAs instead of in
     // a burst after the barrier, where both waves of a SIMD issue theirs at the
     // same time and the MFMA pipe idles: 0.711 -> 0.694 ms (C128 R32 fwd),
     // 0.368 -> 0.357 ms (C256 R16), tools/conv_ab.py on MI355X; 4 MFMAs per
     // piece (over-asking the 16 left after the fragment reads): 0.680 / 0.348 ms
-    glds_frags<KT, GN>(lds, (s + 1) % NST, wr, wc, r, h, Fn);
-#ifndef PCFM_EXP_CNOMFMA
-    glds_mfma<KT>(Fc, acc);
-#else
-    acc[0][0][0] += (float)Fc[0][0][0];
-#endif
+    frags((s + 1) % NST, Fn);
+    glds_mfma(Fc, acc);
     // unconditional (same basic block as the MFMAs, so the scheduler can place
     // the pieces between them): past the last step it reloads the final
-    // step's data into the buffer step s just drained (never read again)
-#ifndef PCFM_EXP_CNODMA
-    // the buffer step s just drained (its fragments were read in step s - 1)
+    // step's data into the buffer step s just drained (never read again; its
+    // fragments were read in step s - 1)
     issue(min(s + NST, nsteps - 1), s % NST);
-#endif
 #pragma unroll
     for (int g = 0; g < 4 * (KT / 16); ++g) {
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -848,26 +827,10 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
     }
 #pragma unroll
     for (int g = 0; g < G::APW + G::BPW; ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x008, PCFM_CONV_DMA_LATE, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);  // MFMAs per LDS-DMA piece
       __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
     }
     __builtin_amdgcn_sched_group_barrier(0x008, 8 * (KT / 16), 0);
-#else
-    static_assert(NST == 3, "the burst-issue schedule needs three stages");
-#ifndef PCFM_EXP_NOLOAD
-    if (s + 3 < nsteps) issue(s + 3, s % kGStages);
-#endif
-    glds_frags<KT, GN>(lds, (s + 1) % kGStages, wr, wc, r, h, Fn);
-    glds_mfma<KT>(Fc, acc);
-    // reads of step s+1 interleaved with the first MFMAs of step s (two
-    // ds_read_b128 per MFMA gap are free, microarch guide "LDS")
-#pragma unroll
-    for (int g = 0; g < 4 * (KT / 16); ++g) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, 12 * (KT / 16) - 4 * (KT / 16), 0);
-#endif
   };
   int s = 0;
   for (; s + 2 < nsteps; s += 2) {
@@ -876,73 +839,19 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
   }
   if (s + 1 < nsteps) {
     step(s, F0, F1);
-    glds_mfma<KT>(F1, acc);
+    glds_mfma(F1, acc);
   } else {
-    glds_mfma<KT>(F0, acc);
+    glds_mfma(F0, acc);
   }
   // the interleaved schedule issues (redundant) pieces in the last steps too:
   // none may still be writing LDS when the wave ends
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#else
-  issue(0, 0);
-  if (nsteps > 1) issue(1, 1);
-  for (int s = 0; s < nsteps; ++s) {
-    // stage s landed (this wave's pieces of it): leave stage s+1's in flight
-    if (s + 1 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::APW + G::BPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // everyone's stage s landed; stage s-1 reads done
-#ifndef PCFM_EXP_NOLOAD
-    if (s + 2 < nsteps) issue(s + 2, (s + 2) % kGStages);
-#endif
-    const uint8_t* base = lds + (s % kGStages) * G::STAGE;
-#pragma unroll
-    for (int kk = 0; kk < KT / 16; ++kk) {
-      const int kc = 2 * kk + h;
-      bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int row = wr * 64 + i * 32 + r;
-        const int off = row * G::RB + ((kc ^ G::swz(row)) << 4);
-        ah[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + off));
-        al[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + G::A + off));
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int row = wc * 64 + j * 32 + r;
-        const int off = 2 * G::A + row * G::RB + ((kc ^ G::swz(row)) << 4);
-        bh[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + off));
-        bl[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(base + G::B + off));
-      }
-#ifdef PCFM_EXP_NOMFMA
-      acc[0][0][kk] += (float)(ah[0][0] + al[0][1] + ah[1][2] + al[1][3] + bh[0][4] + bl[0][5] +
-                               bh[1][6] + bl[1][7]);
-      continue;
-#endif
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-    }
-  }
-#endif
   }
   float* __restrict__ yb = S == 1 ? y + (size_t)b * M * V : part + ((size_t)sp * nb + b) * M * V;
+  // this lane's output column per j: dense y[b][m][v0 + col], list y[g / V][m][g % V]
   float biasv[2][16];
 #pragma unroll
   for (int i = 0; i < 2; ++i) load_bias16(S == 1 ? bias : nullptr, m0 + wr * 64 + i * 32, h, M, biasv[i]);
-  // this lane's output column per j: dense y[b][m][v0 + col], list y[g / V][m][g % V]
   float* ycol[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
@@ -963,30 +872,9 @@ __global__ void __launch_bounds__(GN * 2)  // GK<KT, GN>::NW = GN / 32 waves
       for (int e = 0; e < 16; ++e) {
         const int m = m0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
         if (ycol[j] != nullptr) {
-#ifndef PCFM_CONV_CACHED_STORE  // streamed: same-box bench 33.70 -> 33.57 ms/step
           nt_st(acc[i][j][e] + biasv[i][e], ycol[j] + (size_t)m * V);
-#else
-          ycol[j][(size_t)m * V] = acc[i][j][e] + biasv[i][e];
-#endif
         }
       }
-}
-
-// LDS-DMA as inline asm: hipcc does not see it, so it inserts no vmcnt(0)
-// before the step's LDS reads (it does for __builtin_amdgcn_global_load_lds
-// here, which serialises the prefetch with the compute); completion is waited
-// for by hand.  M0 is set and restored inside the statement.
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-__device__ __forceinline__ void glds16_asm(const void* g, uint32_t lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g), "s"(lds)
-      : "memory");
 }
 
 // ---------------------------------------------------------------------------
@@ -1019,7 +907,7 @@ __global__ void __launch_bounds__(512)
     conv3_igemm_win_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ wh,
                            const float* __restrict__ bias, float* __restrict__ y, int K, int M,
                            int R, int S, float* __restrict__ part) {
-  using G = GK<32, kGN>;
+  using G = GK<kGN>;
   constexpr int kAStage = 2 * G::A;                 // weight slice hi | lo: 16 KiB
   constexpr int kWinImg = kWinRowsMax * G::RB;      // 26 KiB per image
   constexpr int NS = kWinStages;                    // weight ring depth
@@ -1028,11 +916,7 @@ __global__ void __launch_bounds__(512)
   uint8_t* aring = lds + 2 * kWinImg;               // kGStages weight stages
   const int V = R * R * R, R2 = R * R, H = R2 + R + 1, WR = win_rows(R);
   const int nmt = M / kGM, nvt = V / kGN;
-  int id = (int)blockIdx.x;
-  {
-    const int nwg = (int)gridDim.x, q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-    id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-  }
+  int id = xcd_deal((int)blockIdx.x, (int)gridDim.x);
   const int nb = (int)gridDim.x / (S * nmt * nvt);
   const int m0 = (id % nmt) * kGM;
   id /= nmt;
@@ -1048,47 +932,22 @@ __global__ void __launch_bounds__(512)
   const size_t bV = (size_t)b * V;
   const uint32_t lds_win = lds_addr(win), lds_ring = lds_addr(aring);
 
-  // weight pieces of this wave: I = 2 w + q (image I / API), as the LDS-DMA kernel
   const uint16_t* abase[G::APW];
-#pragma unroll
-  for (int q = 0; q < G::APW; ++q) {
-    const int I = G::APW * w + q;
-    const int row = (I % G::API) * G::RPP + prow;
-    abase[q] = wh + (kSplitLo * (I / G::API)) + (size_t)(m0 + row) * 2 * K +
-               ((pch ^ G::swz(row)) << 3);
-  }
-  // this lane's two B columns (j): tap validity, and their window row H + col
-  uint32_t bval[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int v = v0 + wc * 64 + j * 32 + r;
-    const int x = v / R2, yy = (v / R) % R, z = v % R;
-    const uint32_t ax = (x > 0 ? 1u : 0u) | 2u | (x + 1 < R ? 4u : 0u);
-    const uint32_t ay = (yy > 0 ? 1u : 0u) | 2u | (yy + 1 < R ? 4u : 0u);
-    const uint32_t az = (z > 0 ? 1u : 0u) | 2u | (z + 1 < R ? 4u : 0u);
-    uint32_t m = 0u;
-#pragma unroll
-    for (int tp = 0; tp < 27; ++tp)
-      m |= (((ax >> (tp / 9)) & (ay >> ((tp / 3) % 3)) & (az >> (tp % 3))) & 1u) << tp;
-    bval[j] = m;
-  }
+  weight_bases<G>(wh, wh + kSplitLo, m0, K, w, lane, abase);
+  // this lane's two B columns (j): tap validity (their window row is H + col)
+  const uint32_t bval[2] = {tap_valid27(v0 + wc * 64 + r, R), tap_valid27(v0 + wc * 64 + 32 + r, R)};
 
   auto issue_a = [&](int c0, int tap, int slot) {
-    const int cof = ((c0 >> 5) << 6) + (c0 & 31);
-    const size_t aofs = (size_t)tap * M * 2 * K + cof;
-#pragma unroll
-    for (int q = 0; q < G::APW; ++q) {
-      const int I = G::APW * w + q;
-      glds16_asm(abase[q] + aofs,
-                 lds_ring + slot * kAStage + (I / G::API) * G::A + (I % G::API) * 1024);
-    }
+    issue_weights<G>(abase, tap, c0, M, K, w, [&](const uint16_t* src, int img, int p) {
+      glds16_asm(src, lds_ring + slot * kAStage + img * G::A + p * 1024);
+    });
   };
   // the window of chunk c0: WR rows x 2 images in 1-KiB pieces (16 rows), dealt
   // round-robin to the waves; rows outside the batch volume are clamped (their
   // products are masked)
   const int wpieces = 2 * (WR / 16);
   auto issue_win = [&](int c0) {
-    const int cof = ((c0 >> 5) << 6) + (c0 & 31);
+    const int cof = split_cof(c0);
     for (int P = w; P < wpieces; P += 8) {  // wave-uniform loop
       const int img = P / (WR / 16), pr = P % (WR / 16);
       const int row = pr * 16 + prow;
@@ -1100,12 +959,7 @@ __global__ void __launch_bounds__(512)
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+  zero_acc(acc);
 
   for (int ch = ch0; ch < ch1; ++ch) {
     const int c0 = ch * 32;
@@ -1119,27 +973,21 @@ __global__ void __launch_bounds__(512)
     for (int q = 0; q < NS - 1; ++q) issue_a(c0, q, q);
     // B fragments (from the window, which stays put during the chunk) read one
     // step ahead: step s + 1's while step s's MFMAs run
-    auto read_b = [&](int s, bf16x8 (&Bf)[2][4]) {
-      const int dx = s / 9 - 1, dy = (s / 3) % 3 - 1, dz = s % 3 - 1;
-      const int toff = H + dx * R2 + dy * R + dz;
+    auto read_b = [&](int s, Frags& F) {
+      const int toff = H + tap_delta(s, R2, R);
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int kc = 2 * kk + h;
+      for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-          const int row = wc * 64 + j * 32 + r + toff;
-          const int off = row * G::RB + ((kc ^ G::swz(row)) << 4);
-          uint4 u0 = *reinterpret_cast<const uint4*>(win + off);
-          uint4 u1 = *reinterpret_cast<const uint4*>(win + kWinImg + off);
+          bf16x8 fh, fl;
+          frag_hl<G>(win, kWinImg, wc * 64 + j * 32 + r + toff, 2 * kk + h, fh, fl);
           const uint32_t mk = ((bval[j] >> s) & 1u) ? 0xFFFFFFFFu : 0u;
-          u0.x &= mk; u0.y &= mk; u0.z &= mk; u0.w &= mk;
-          u1.x &= mk; u1.y &= mk; u1.z &= mk; u1.w &= mk;
-          Bf[kk][j] = __builtin_bit_cast(bf16x8, u0);
-          Bf[kk][2 + j] = __builtin_bit_cast(bf16x8, u1);
+          F[kk].bh[j] = mask_k8(fh, mk, mk, mk);
+          F[kk].bl[j] = mask_k8(fl, mk, mk, mk);
         }
-      }
     };
-    auto step = [&](int s, const bf16x8 (&Bc)[2][4], bf16x8 (&Bn)[2][4]) {
+    // step s: its B fragments are in Fc; its A fragments are read here
+    auto step = [&](int s, Frags& Fc, Frags& Fn) {
       // this wave's pieces of step s (and the window) landed; step s + 1's stay
       // in flight; the barrier makes everyone's visible and ends the reads of
       // step s - 1, whose stage step s + 2 refills
@@ -1156,40 +1004,20 @@ __global__ void __launch_bounds__(512)
       __builtin_amdgcn_s_barrier();
       if (s + NS - 1 < 27) issue_a(c0, s + NS - 1, (s + NS - 1) % NS);
       const uint8_t* ab = aring + (s % NS) * kAStage;
-      if (s + 1 < 27) read_b(s + 1, Bn);
+      if (s + 1 < 27) read_b(s + 1, Fn);
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        const int kc = 2 * kk + h;
-        bf16x8 ah[2], al[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const int row = wr * 64 + i * 32 + r;
-          const int off = row * G::RB + ((kc ^ G::swz(row)) << 4);
-          ah[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ab + off));
-          al[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ab + G::A + off));
-        }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], Bc[kk][j], acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], Bc[kk][2 + j], acc[i][j], 0, 0, 0);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int j = 0; j < 2; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], Bc[kk][j], acc[i][j], 0, 0, 0);
+          frag_hl<G>(ab, G::A, wr * 64 + i * 32 + r, 2 * kk + h, Fc[kk].ah[i], Fc[kk].al[i]);
+        mfma_x3(Fc[kk].ah, Fc[kk].al, Fc[kk].bh, Fc[kk].bl, acc);
       }
     };
     // the window landed (this wave's pieces: everything but step 1's weights),
     // then everyone's: step 0's B fragments
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NS - 1) * G::APW) : "memory");
     __builtin_amdgcn_s_barrier();
-    bf16x8 B0[2][4], B1[2][4];
+    Frags B0, B1;
     read_b(0, B0);
     int s = 0;
     for (; s + 1 < 27; s += 2) {
@@ -1199,18 +1027,8 @@ __global__ void __launch_bounds__(512)
     step(s, B0, B1);  // s = 26
   }
   float* __restrict__ yb = S == 1 ? y + (size_t)b * M * V : part + ((size_t)sp * nb + b) * M * V;
-  float biasv[2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) load_bias16(S == 1 ? bias : nullptr, m0 + wr * 64 + i * 32, h, M, biasv[i]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        nt_st(acc[i][j][e] + biasv[i][e], yb + (size_t)m * V + v0 + wc * 64 + j * 32 + r);
-      }
+  tile_epilogue(acc, S == 1 ? bias : nullptr, m0 + wr * 64, h, M, V,
+                [&](int j) { return yb + v0 + wc * 64 + j * 32 + r; });
 }
 
 // ---------------------------------------------------------------------------
@@ -1243,7 +1061,7 @@ struct SlabGeo {
   static constexpr int WQ = (PIECES + 7) / 8;        // slab pieces per wave (6)
   static constexpr int IMG = NSP * 64;               // bytes of one image (64-B rows)
   static constexpr int SLAB = 2 * IMG;
-  static constexpr int ASTAGE = GK<32>::STAGE - 2 * GK<32>::B;  // A hi | lo: 16 KiB
+  static constexpr int ASTAGE = 2 * GK<>::A;         // A hi | lo: 16 KiB
   static constexpr int LDS = 3 * ASTAGE + 2 * SLAB;
   static_assert(R * YT == 256 && LDS <= 160 * 1024 && WQ <= 9, "slab geometry");
 };
@@ -1253,18 +1071,14 @@ __global__ void __launch_bounds__(512)
     conv3_igemm_slab_kernel(const uint16_t* __restrict__ xh, const uint16_t* __restrict__ wh,
                             const uint16_t* __restrict__ zrow, const float* __restrict__ bias,
                             float* __restrict__ y, int K, int M) {
-  using G = GK<32>;
+  using G = GK<>;
   using SG = SlabGeo<R_>;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   uint8_t* aring = lds;                       // 3 x (A hi | A lo)
   uint8_t* slabs = lds + 3 * SG::ASTAGE;      // 2 x (slab hi | slab lo)
   constexpr int R = SG::R, R2 = SG::R2, V = SG::V;
   const int nmt = M / kGM, nvt = V / 256;
-  int id = (int)blockIdx.x;
-  {
-    const int nwg = (int)gridDim.x, q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-    id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-  }
+  int id = xcd_deal((int)blockIdx.x, (int)gridDim.x);
   const int m0 = (id % nmt) * kGM;
   id /= nmt;
   const int v0 = (id % nvt) * 256;
@@ -1275,16 +1089,8 @@ __global__ void __launch_bounds__(512)
   const int wr = w / 4, wc = w % 4, r = lane & 31, h = lane >> 5;
   const int nck = K / 32, T = 27 * nck;
   const int prow = lane / G::CPR, pch = lane % G::CPR;
-  const uint16_t* __restrict__ wl = wh + kSplitLo;
-
-  // A pieces (as the LDS-DMA kernel): I = APW w + q -> image I / API, rows (I % API) * RPP + prow
   const uint16_t* abase[G::APW];
-#pragma unroll
-  for (int q = 0; q < G::APW; ++q) {
-    const int I = G::APW * w + q;
-    const int row = (I % G::API) * G::RPP + prow;
-    abase[q] = ((I / G::API) ? wl : wh) + (size_t)(m0 + row) * 2 * K + ((pch ^ G::swz(row)) << 3);
-  }
+  weight_bases<G>(wh, wh + kSplitLo, m0, K, w, lane, abase);
   // this lane's B fragment rows at tap (0, 0): slab row (yl + 1) SZ + z + 1
   int brow[2];
 #pragma unroll
@@ -1321,48 +1127,21 @@ __global__ void __launch_bounds__(512)
            slabs + sbuf * SG::SLAB + img * SG::IMG + P * 1024);
   };
   auto a_pieces = [&](int s, int buf) {
-    const int c0 = (s / 27) * 32, tap = s % 27;
-    const int cof = ((c0 >> 5) << 6) + (c0 & 31);
-    const size_t aofs = (size_t)tap * M * 2 * K + cof;
-#pragma unroll
-    for (int q = 0; q < G::APW; ++q) {
-      const int I = G::APW * w + q;
-      glds16(abase[q] + aofs, aring + buf * SG::ASTAGE + (I / G::API) * G::A + (I % G::API) * 1024);
-    }
+    issue_weights<G>(abase, s % 27, (s / 27) * 32, M, K, w, [&](const uint16_t* src, int img, int p) {
+      glds16(src, aring + buf * SG::ASTAGE + img * G::A + p * 1024);
+    });
   };
   // fragments of a step: A from ring slot `ring`, B from slab buffer `sbuf` at
   // the offset of the slab's tap u = 3 (dy + 1) + dz + 1
-  auto frags = [&](int ring, int u, int sbuf, bf16x8 (&F)[2][8]) {
-    const uint8_t* ab = aring + ring * SG::ASTAGE;
+  auto frags = [&](int ring, int u, int sbuf, Frags& F) {
     const int toff = (u / 3 - 1) * SG::SZ + (u % 3 - 1);
-    const uint8_t* sb = slabs + sbuf * SG::SLAB;
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int kc = 2 * kk + h;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int row = wr * 64 + i * 32 + r;
-        const int off = row * G::RB + ((kc ^ G::swz(row)) << 4);
-        F[kk][i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ab + off));
-        F[kk][2 + i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ab + G::A + off));
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int row = brow[j] + toff;
-        const int off = row * G::RB + ((kc ^ G::swz(row)) << 4);
-        F[kk][4 + j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sb + off));
-        F[kk][6 + j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sb + SG::IMG + off));
-      }
-    }
+    const int rows[2] = {brow[0] + toff, brow[1] + toff};
+    read_frags<G>(aring + ring * SG::ASTAGE, wr * 64 + r, slabs + sbuf * SG::SLAB, SG::IMG, rows, h,
+                  F);
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+  zero_acc(acc);
 
   const int nslab = 3 * nck;  // even (nck even: the launcher's condition)
   // prologue: slab 0 whole, A of steps 0..2
@@ -1373,21 +1152,21 @@ __global__ void __launch_bounds__(512)
   a_pieces(2, 2);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
-  bf16x8 F[2][2][8];
+  Frags F[2];
   frags(0, 0, 0, F[0]);
   // step s: its fragments are in Fc; read step s + 1's (past the end: unused),
   // run step s's MFMAs, DMA A of step s + 3 into ring s % 3 and one piece of
   // the next slab.  Every step issues exactly APW + 1 pieces (the extra ones
   // re-issue data that is already there or never read again), so the wait at
   // the next step's top is one immediate.
-  auto step = [&](int s, bf16x8 (&Fc)[2][8], bf16x8 (&Fn)[2][8]) {
+  auto step = [&](int s, Frags& Fc, Frags& Fn) {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(G::APW + 1) : "memory");
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
     __builtin_amdgcn_s_barrier();
     const int sl = s / 9, u = s - 9 * sl;
     const int un = u == 8 ? 0 : u + 1;
     frags((s + 1) % 3, un, (sl + (u == 8 ? 1 : 0)) & 1, Fn);
-    glds_mfma<32>(Fc, acc);
+    frags_mfma(Fc, acc);
     a_pieces(min(s + 3, T - 1), s % 3);
     slab_piece(min(sl + 1, nslab - 1), min(u, SG::WQ - 1), (sl + 1) & 1);
 #pragma unroll
@@ -1409,20 +1188,8 @@ __global__ void __launch_bounds__(512)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // no DMA may outlive the wave
 
   float* __restrict__ yb = y + (size_t)b * M * V;
-  float biasv[2][16];
-#pragma unroll
-  for (int i = 0; i < 2; ++i) load_bias16(bias, m0 + wr * 64 + i * 32, h, M, biasv[i]);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      float* ycol = yb + v0 + wc * 64 + j * 32 + r;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
-        nt_st(acc[i][j][e] + biasv[i][e], ycol + (size_t)m * V);
-      }
-    }
+  tile_epilogue(acc, bias, m0 + wr * 64, h, M, V,
+                [&](int j) { return yb + v0 + wc * 64 + j * 32 + r; });
 }
 
 // (Measured and removed: a BRICK form -- 256 output voxels a 2x4x32 / 2x8x16
@@ -1454,11 +1221,7 @@ __global__ void __launch_bounds__(256)
   uint8_t* iBl = lds + 3 * kWV * 256;
   const int V = R * R * R, R2 = R * R;
   const int nco = cout / kMT;
-  int id = (int)blockIdx.x;
-  {
-    const int nwg = (int)gridDim.x, q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-    id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-  }
+  int id = xcd_deal((int)blockIdx.x, (int)gridDim.x);
   const int tap = id % 27;
   id /= 27;
   const int sp = id % S;
@@ -1508,7 +1271,7 @@ __global__ void __launch_bounds__(256)
     }
   };
 
-  f32x16 acc[2][2];
+  f32x16 acc[2][2];  // (zeroed in place: zero_acc changes this kernel's register allocation)
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1522,21 +1285,10 @@ __global__ void __launch_bounds__(256)
   }
   __syncthreads();
   for (long long ks = k0; ks < k1; ++ks) {
-#ifndef PCFM_EXP_WG_NOLOAD
     if (ks + 1 < k1) load(ks + 1);
-#endif
 #pragma unroll
     for (int kk = 0; kk < kWV / 16; ++kk) {
       bf16x8 ah[2], al[2], bh[2], bl[2];
-#ifdef PCFM_EXP_WG_NOLDSREAD
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        ah[i] = __builtin_bit_cast(bf16x8, sv_get<4>(rah, i));
-        al[i] = __builtin_bit_cast(bf16x8, sv_get<4>(ral, i));
-        bh[i] = __builtin_bit_cast(bf16x8, sv_get<4>(rbh, i));
-        bl[i] = __builtin_bit_cast(bf16x8, sv_get<4>(rbl, i));
-      }
-#else
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         ah[i] = tr_operand(iAh, kk, wr * 64 + i * 32, lane);
@@ -1547,15 +1299,8 @@ __global__ void __launch_bounds__(256)
         bh[j] = tr_operand(iBh, kk, wc * 64 + j * 32, lane);
         bl[j] = tr_operand(iBl, kk, wc * 64 + j * 32, lane);
       }
-#endif
-#ifdef PCFM_EXP_WG_NOMFMA
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j][kk] += (float)ah[i][kk] + (float)bh[j][kk] + (float)al[i][kk] + (float)bl[j][kk];
-      continue;
-#endif
+      // mfma_x3's sequence, in place: through the call this kernel's code
+      // object changes (scheduling only), and it is kept bit for bit
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1572,11 +1317,9 @@ __global__ void __launch_bounds__(256)
         for (int j = 0; j < 2; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
     }
-#ifndef PCFM_EXP_WG_NOLOAD
     __syncthreads();
     if (ks + 1 < k1) store();
     __syncthreads();
-#endif
   }
   float* pb = part + ((size_t)sp * 27 + tap) * cout * cin;
   const int h = lane >> 5, r = lane & 31;
@@ -1625,15 +1368,6 @@ __device__ __forceinline__ bf16x8 tr_operand_rows(const uint8_t* img, int row0, 
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7));
 }
 
-__device__ __forceinline__ bf16x8 mask_k8(bf16x8 v, uint32_t m0, uint32_t m12, uint32_t m3) {
-  uint4 u = __builtin_bit_cast(uint4, v);
-  u.x &= m0;
-  u.y &= m12;
-  u.z &= m12;
-  u.w &= m3;
-  return __builtin_bit_cast(bf16x8, u);
-}
-
 // Chunk lists of the masked weight gradient: for each (pair, split sp), the
 // 64-voxel chunks c = sp, sp + S, sp + 2S, ... whose X operand for that pair is
 // nonzero (conv3_occupancy_kernel's cmask), in increasing order -- exactly the
@@ -1677,11 +1411,7 @@ __global__ void __launch_bounds__(kW3Threads)
   PCFM_CLAIM_VGPRS(167);
   const int V = R * R * R, R2 = R * R;
   const int nco = cout / kMT;
-  int id = (int)blockIdx.x;
-  {
-    const int nwg = (int)gridDim.x, q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-    id = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-  }
+  int id = xcd_deal((int)blockIdx.x, (int)gridDim.x);
   const int pair = id % 9;
   id /= 9;
   const int sp = id % S;
@@ -1747,7 +1477,7 @@ __global__ void __launch_bounds__(kW3Threads)
     for (int q = 0; q < kW3Q; ++q) issue_q(q, b, v0, buf);
   };
 
-  f32x16 acc[2][2];
+  f32x16 acc[2][2];  // (zeroed in place: zero_acc changes this kernel's register allocation)
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -1779,9 +1509,7 @@ __global__ void __launch_bounds__(kW3Threads)
     if (more) cnext = chunk_of(st + 1);
     const int nb = cnext / cpb, nv0 = (cnext % cpb) * kWV;
     uint8_t* nbuf = lds + ((st + 1) & 1) * kW3Buf;
-#ifndef PCFM_EXP_WG_NOLOAD
     if (more) issue(nb, nv0, nbuf);
-#endif
     const uint8_t* iAh = cur;
     const uint8_t* iAl = cur + kW3AImg;
     const uint8_t* iBh = cur + 2 * kW3AImg;
@@ -1816,21 +1544,7 @@ __global__ void __launch_bounds__(kW3Threads)
         bl[j] = mask_k8(tr_operand_rows(iBl, kk * 16 + 1 + dz, wc * 64 + j * 32, lane), m0, mall,
                         m3);
       }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+      mfma_x3(ah, al, bh, bl, acc);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // step ks+1 landed (this wave's pieces)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1905,11 +1619,7 @@ __global__ void __launch_bounds__(256)
 #define PCFM_WGRAD3_BLOCKS 2  // blocks per CU the three-tap split aims for
 #endif
 bool conv3_wgrad3_ok(int R) {
-#ifdef PCFM_WGRAD_NO3
-  return false;
-#else
   return R >= 8 && (R & (R - 1)) == 0;  // 8-voxel z runs, shift-decoded voxel index
-#endif
 }
 
 int conv3_wgrad_splits(int B, int cin, int cout, int R) {
@@ -1950,6 +1660,178 @@ bool conv3_shape_ok(int b, int cin, int cout, int r) {
 
 using namespace pcfm;
 
+// ---------------------------------------------------------------------------
+// Host side.  Every decision a launch and its workspace query share is taken
+// once, in a pure plan function both read; every buffer with several arrays
+// has its offsets in one layout struct (the layouts' documentation: pcfm.h).
+// ---------------------------------------------------------------------------
+
+// Measurement and test knobs (environment), read at the top of an entry point.
+struct Knobs {
+  // read per call: tests compare both settings in one process
+  bool slab;     // PCFM_CONV_SLAB=0: dense r = 32 / 16 on the LDS-DMA kernel (B refetched per tap)
+  bool win;      // PCFM_CONV_WIN=0: split-K r = 8 on the LDS-DMA kernel
+  // The list forms over single voxels (lists 2 / 3) instead of 32-voxel chunks
+  // (lists 0 / 1): PCFM_LIST_VOX bit 0 = backward-data (which 0), bit 1 =
+  // forward (which 1); default 3.  At the C2 stages an occupied chunk holds
+  // 27 % (r = 32) / 36 % (r = 16) occupied voxels, and a listed forward chunk
+  // 49 % / 61 % active voxels.
+  int list_vox;
+  // read once per process (A/B runs set them before the library loads).
+  // List-form tile in voxels per direction, PCFM_LIST_GN_BWD / _FWD = 256 or
+  // 128.  The backward-data's list (the occupied voxels, 12 % at r = 32, 21 %
+  // at r = 16) fills only ~120 / ~110 blocks of 256 voxels -- half the CUs
+  // idle -- so it takes 128-voxel tiles: 0.89 -> 0.70 ms/step; the forward's
+  // longer list (30 % / 50 %) is slower on them (1.17 -> 1.34),
+  // profiles/r06_ab_list_gn128.jsonl.  PCFM_LIST_NST: 3 / 2 LDS-DMA stages at
+  // 128 (2: two blocks per CU; measured slower, 0.85 ms).
+  int list_gn[2], list_nst;
+  bool list_zrow;    // PCFM_LIST_ZROW=0: the forward list form reads every in-volume row
+  bool wgrad_kskip;  // PCFM_WGRAD_KSKIP=0: the masked weight gradient without K-slice masks
+};
+
+static bool env_on(const char* name) {  // on unless set to 0...
+  const char* e = getenv(name);
+  return e == nullptr || e[0] != '0';
+}
+
+static Knobs read_knobs() {
+  static const Knobs once = [] {
+    Knobs k{};
+    const char* bwd = getenv("PCFM_LIST_GN_BWD");
+    const char* fwd = getenv("PCFM_LIST_GN_FWD");
+    k.list_gn[0] = bwd != nullptr ? (atoi(bwd) == 128 ? 128 : 256) : 128;
+    k.list_gn[1] = fwd != nullptr ? (atoi(fwd) == 128 ? 128 : 256) : 256;
+    const char* nst = getenv("PCFM_LIST_NST");
+    k.list_nst = nst != nullptr && atoi(nst) == 2 ? 2 : 3;
+    k.list_zrow = env_on("PCFM_LIST_ZROW");
+    k.wgrad_kskip = env_on("PCFM_WGRAD_KSKIP");
+    return k;
+  }();
+  Knobs k = once;
+  k.slab = env_on("PCFM_CONV_SLAB");
+  k.win = env_on("PCFM_CONV_WIN");
+  const char* lv = getenv("PCFM_LIST_VOX");
+  k.list_vox = lv == nullptr ? 3 : (atoi(lv) & 3);
+  return k;
+}
+
+// int32 offsets of the arrays in pcfm_conv3d_vlist's buffer
+struct VlistLayout {
+  size_t tiles, chunks, voxels;  // 256-voxel tiles, 32-voxel chunks, voxels: of all b samples
+  static constexpr size_t counts = 0;  // [4], padded to 64
+  size_t tcount;                       // per-tile counts / offsets of lists 0, 1: [2][tiles]
+  size_t list[4];                      // lists 0, 1 [chunks each], 2, 3 [voxels each]
+  size_t tcount2;                      // per-tile counts / offsets of lists 2, 3: [2][tiles]
+  size_t bits[2];                      // bitmaps of lists 2, 3 [chunks words each]
+  size_t total;
+  VlistLayout(int b, int r) {
+    voxels = (size_t)b * r * r * r;
+    tiles = voxels / 256;
+    chunks = voxels / kChunk;
+    tcount = 64;
+    list[0] = tcount + 2 * tiles;
+    list[1] = list[0] + chunks;
+    tcount2 = list[1] + chunks;
+    list[2] = tcount2 + 2 * tiles;
+    list[3] = list[2] + voxels;
+    bits[0] = list[3] + voxels;
+    bits[1] = bits[0] + chunks;
+    total = bits[1] + chunks;
+  }
+};
+
+// uint32 offsets of the three mask arrays in pcfm_conv3d_occupancy's buffer
+struct OccLayout {
+  static constexpr size_t tmask = 0;  // [b][V / 256]
+  size_t cmask, kmask, total;         // [b][V / 64], [b][V / 16]
+  OccLayout(int b, int r) {
+    const size_t v = (size_t)r * r * r;
+    cmask = (size_t)b * (v / 256);
+    kmask = cmask + (size_t)b * (v / 64);
+    total = kmask + (size_t)b * (v / 16);
+  }
+};
+
+// The forward / backward-data GEMM of a supported shape (b > 0): which kernel,
+// how many K splits, the launch and the workspace.
+enum class IgemmForm { kSlab, kWindow, kDma, kDmaList128 };
+struct IgemmOptions {
+  bool masked = false;   // tile masks given (pcfm_conv3d_igemm_cl_occ)
+  bool listed = false;   // a voxel or chunk list given (pcfm_conv3d_igemm_cl_list)
+  int list_gn = kGN;     // the list form's tile (Knobs::list_gn)
+  bool slab = true, win = true;  // Knobs
+};
+struct IgemmPlan {
+  IgemmForm form;
+  int S;            // K splits; S > 1: partials in the workspace, summed by conv3_ksum_kernel
+  bool sparse;      // masks / lists apply: unsplit launches only (a split's K
+                    // range is a fixed share of all 27 taps; the list form is unsplit)
+  unsigned grid, block;
+  size_t lds;       // dynamic LDS
+  size_t ws_bytes;  // 1: none needed
+};
+
+static IgemmPlan plan_igemm(int b, int cin, int cout, int r, const IgemmOptions& o) {
+  IgemmPlan p{};
+  const int V = r * r * r;
+  // small grids (r = 8) split K so that about one block per CU runs, >= 16
+  // K-steps of 16 channels per split, ordered reduce.  Independent of the
+  // options: the workspace query has none.
+  const long long items = (long long)(V / kGN) * (cout / kGM) * b;
+  const long long nall = 27LL * (cin / 16);
+  long long s = std::max(1LL, (long long)kCUs / std::max(1LL, items));
+  s = std::min(s, std::max(1LL, nall / 16));
+  p.S = (int)std::min(s, 8LL);
+  p.ws_bytes = p.S == 1 ? 1 : (size_t)p.S * b * cout * V * sizeof(float);
+  p.sparse = p.S == 1 && (o.masked || o.listed);
+  p.form = IgemmForm::kDma;
+  p.grid = (unsigned)(items * p.S);
+  p.block = 512;
+  if (p.S == 1 && !p.sparse && (r == 32 || r == 16) && o.slab) {
+    p.form = IgemmForm::kSlab;
+    p.lds = r == 32 ? SlabGeo<32>::LDS : SlabGeo<16>::LDS;
+  } else if (!p.sparse && r <= 8 && win_rows(r) <= kWinRowsMax && (cin / 32) % p.S == 0 && o.win) {
+    p.form = IgemmForm::kWindow;  // whole 32-channel chunks per split
+    p.lds = 2 * (size_t)kWinRowsMax * 64 + (size_t)kWinStages * 2 * kGM * 64;
+  } else if (p.S == 1 && o.listed && o.list_gn == 128) {
+    p.form = IgemmForm::kDmaList128;  // twice the blocks, 4 waves each
+    p.grid = (unsigned)((long long)(V / 128) * (cout / kGM) * b);
+    p.block = 256;
+  }
+  return p;
+}
+
+// The weight gradient of a supported shape: kernel, splits, workspace parts.
+struct WgradPlan {
+  bool three;         // conv3_wgrad3_kernel (else conv3_wgrad_cl_kernel)
+  int S, cap;         // splits; 64-voxel chunks per split at most (a list row)
+  size_t part_bytes;  // S partials [27][cout][cin] fp32
+  size_t list_bytes, count_bytes;  // the masked form's chunk lists [9][S][cap] and counts [9][S]
+  size_t lds, lds_kmask;  // two buffers; with a split's K-slice mask words behind them
+  bool kmask_fits;    // where they do not fit the kernel runs without them (the
+                      // skip only drops exact-zero products)
+  unsigned grid, block;
+};
+
+static WgradPlan plan_wgrad(int b, int cin, int cout, int r) {
+  WgradPlan p{};
+  p.three = conv3_wgrad3_ok(r);
+  p.S = conv3_wgrad_splits(b, cin, cout, r);
+  const long long nchunk = (long long)b * r * r * r / kWV;
+  p.cap = (int)((nchunk + p.S - 1) / p.S);
+  p.part_bytes = (size_t)p.S * 27 * cout * cin * sizeof(float);
+  p.list_bytes = (size_t)9 * p.S * p.cap * sizeof(int);
+  p.count_bytes = (size_t)9 * p.S * sizeof(int);
+  p.lds = p.three ? 2 * (size_t)kW3Buf : 0;
+  p.lds_kmask = p.lds + (size_t)p.cap * 16;
+  p.kmask_fits = p.lds_kmask <= (size_t)kLdsBytesMax;
+  const int tiles = 27 * (cout / kMT) * (cin / kMT);
+  p.grid = (unsigned)(p.three ? tiles / 3 * p.S : tiles * p.S);
+  p.block = p.three ? kW3Threads : 256;
+  return p;
+}
+
 extern "C" size_t pcfm_conv3d_weight_bytes(int cout, int cin) {
   if (cout <= 0 || cin <= 0) return 0;
   return (size_t)2 * 27 * cout * cin * sizeof(uint16_t);
@@ -1970,10 +1852,6 @@ extern "C" int pcfm_conv3d_prep_weight(const float* w, int cout, int cin, int tr
 extern "C" int pcfm_conv3d_supported(int b, int cin, int cout, int r) {
   return conv3_shape_ok(b, cin, cout, r) ? 1 : 0;
 }
-
-#ifndef PCFM_CONV_KT
-#define PCFM_CONV_KT 64
-#endif
 
 // One 256-B zero buffer per device (the LDS-DMA source of out-of-grid rows).
 static const uint16_t* zero_row() {
@@ -1996,7 +1874,7 @@ static size_t split_bytes_al(int b, int cin, int r) {
 }
 
 extern "C" size_t pcfm_conv3d_igemm_workspace_bytes(int b, int cin, int cout, int r) {
-  if (!conv3_shape_ok(b, cin, cout, r) || cin % 64 != 0) return 0;
+  if (!conv3_shape_ok(b, cin, cout, r)) return 0;
   return split_bytes_al(b, cin, r) + pcfm_conv3d_igemm_cl_workspace_bytes(b, cin, cout, r);
 }
 
@@ -2017,32 +1895,31 @@ extern "C" int pcfm_conv3d_igemm(const float* x, const void* wsplit, const float
                                               (uint8_t*)ws + so, ws_bytes - so, stream);
 }
 
-static size_t wgrad_partial_bytes(int b, int cin, int cout, int r) {
-  return (size_t)conv3_wgrad_splits(b, cin, cout, r) * 27 * cout * cin * sizeof(float);
+static bool wgrad_shape_ok(int b, int cin, int cout, int r) {
+  return b > 0 && conv3_shape_ok(b, cin, cout, r) && cin % kMT == 0;
 }
 
 extern "C" size_t pcfm_conv3d_wgrad_workspace_bytes(int b, int cin, int cout, int r) {
-  if (b <= 0 || !conv3_shape_ok(b, cin, cout, r) || cin % kMT != 0) return 0;
+  if (!wgrad_shape_ok(b, cin, cout, r)) return 0;
   // split-operand partials, plus room for split(x) and split(grad_y) when the
   // fp32 entry point (pcfm_conv3d_wgrad) makes them itself
   const size_t v = (size_t)r * r * r;
-  return wgrad_partial_bytes(b, cin, cout, r) + 4 * (size_t)b * v * (cin + cout);
+  return plan_wgrad(b, cin, cout, r).part_bytes + 4 * (size_t)b * v * (cin + cout);
 }
 
 extern "C" int pcfm_conv3d_wgrad(const float* x, const float* grad_y, int b, int cin, int cout,
                                  int r, float* grad_w, void* ws, size_t ws_bytes, void* stream) {
-  PCFM_CHECK_ARG(b > 0 && conv3_shape_ok(b, cin, cout, r) && cin % kMT == 0,
+  PCFM_CHECK_ARG(wgrad_shape_ok(b, cin, cout, r),
                  "conv3d_wgrad: unsupported shape b=%d cin=%d cout=%d r=%d", b, cin, cout, r);
   const size_t need = pcfm_conv3d_wgrad_workspace_bytes(b, cin, cout, r);
   PCFM_CHECK_ARG(ws_bytes >= need, "conv3d_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
   const size_t v = (size_t)r * r * r;
-  char* xs = (char*)ws + wgrad_partial_bytes(b, cin, cout, r);
+  const size_t pb = plan_wgrad(b, cin, cout, r).part_bytes;
+  char* xs = (char*)ws + pb;
   char* gys = xs + 4 * (size_t)b * v * cin;
   int rc = pcfm_conv3d_split(x, b, cin, r, xs, stream);
   if (rc == PCFM_OK) rc = pcfm_conv3d_split(grad_y, b, cout, r, gys, stream);
-  if (rc == PCFM_OK)
-    rc = pcfm_conv3d_wgrad_cl(xs, gys, b, cin, cout, r, grad_w, ws,
-                              wgrad_partial_bytes(b, cin, cout, r), stream);
+  if (rc == PCFM_OK) rc = pcfm_conv3d_wgrad_cl(xs, gys, b, cin, cout, r, grad_w, ws, pb, stream);
   return rc;
 }
 
@@ -2061,206 +1938,101 @@ extern "C" int pcfm_conv3d_split(const float* x, int b, int c, int r, void* xs, 
   return check_launch("conv3d_split");
 }
 
-// split-K count of the 64 x 64 tile path (small grids: r = 8): enough blocks
-// to fill the chip, >= 8 K-steps each
-static int igemm_splits(int b, int cin, int cout, int r) {
-  const int V = r * r * r;
-  const long long blocks = (long long)(V / 64) * (cout / 64) * b;
-  const long long nall = 27LL * (cin / PCFM_CONV_KT);
-  long long s = std::max(1LL, (4LL * kCUs + blocks - 1) / blocks);
-  s = std::min(s, std::max(1LL, nall / 8));
-  return (int)std::min(s, 8LL);
-}
-
-static bool igemm_big(int b, int cout, int r) {
-  const int V = r * r * r;
-  const long long big_blocks = (long long)(V / 128) * (cout / 128) * b;
-  return big_blocks >= 2 * kCUs;
-}
-
-#ifndef PCFM_CONV_GLDS_MINV
-#define PCFM_CONV_GLDS_MINV 512  // 4096: r = 8 on the 64x64-tile kernel instead
-#endif
-// LDS-DMA kernel applies (128 x 256 tiles); small grids (r = 8) split K so
-// that about one block per CU runs, >= 8 K-steps per split, ordered reduce.
-static bool glds_ok(int cout, int r) {
-  const int V = r * r * r;
-  return V % kGN == 0 && V >= PCFM_CONV_GLDS_MINV && cout % kGM == 0;
-}
-
-static int glds_splits(int b, int cin, int cout, int r) {
-  const int V = r * r * r;
-  const long long items = (long long)(V / kGN) * (cout / kGM) * b;
-  const long long nall = 27LL * (cin / 16);  // K-steps at KT = 16 (the shorter bound)
-  long long s = std::max(1LL, (long long)kCUs / std::max(1LL, items));
-  s = std::min(s, std::max(1LL, nall / 16));
-  return (int)std::min(s, 8LL);
-}
-
 extern "C" size_t pcfm_conv3d_igemm_cl_workspace_bytes(int b, int cin, int cout, int r) {
   if (!conv3_shape_ok(b, cin, cout, r)) return 0;
-  if (b == 0) return 1;
-#ifndef PCFM_CONV_NOGLDS
-  if (glds_ok(cout, r)) {
-    const int S = glds_splits(b, cin, cout, r);
-    return S == 1 ? 1 : (size_t)S * b * cout * r * r * r * sizeof(float);
-  }
-#endif
-  if (igemm_big(b, cout, r)) return 1;
-  const int S = igemm_splits(b, cin, cout, r);
-  return S == 1 ? 1 : (size_t)S * b * cout * r * r * r * sizeof(float);
+  return b == 0 ? 1 : plan_igemm(b, cin, cout, r, IgemmOptions{}).ws_bytes;
 }
 
-
-
-// Slab form of the dense r = 32 / 16 launches (PCFM_CONV_SLAB=0: the LDS-DMA
-// kernel that refetches B per tap)
-static bool conv_slab() {
-  const char* e = getenv("PCFM_CONV_SLAB");  // read per call: tests compare both forms
-  return e == nullptr || e[0] != '0';
+// y = bias + the S partials in split order (split-K launches)
+static void launch_ksum(const float* part, const float* bias, int S, int b, int cout, int V,
+                        float* y, hipStream_t st) {
+  const long long total4 = (long long)b * cout * V / 4;
+  hipLaunchKernelGGL(conv3_ksum_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st,
+                     part, bias, S, cout, V, total4, y);
 }
 
-// Window form of the small-grid split-K launches (PCFM_CONV_WIN=0: the
-// LDS-DMA kernel that refetches B per tap)
-static bool conv_win() {
-  const char* e = getenv("PCFM_CONV_WIN");  // read per call: tests compare both forms
-  return e == nullptr || e[0] != '0';
-}
-
-
-// List-form tile in voxels, per direction (env PCFM_LIST_GN_FWD / _BWD = 256 or
-// 128, read per call: A/B runs).  The backward-data's list (the occupied
-// voxels, 12 % at r = 32, 21 % at r = 16) fills only ~120 / ~110 blocks of
-// 256 voxels -- half the CUs idle -- so it takes 128-voxel tiles: 0.89 -> 0.70
-// ms/step; the forward's longer list (30 % / 50 %) is slower on them (1.17 ->
-// 1.34), profiles/r06_ab_list_gn128.jsonl.  PCFM_LIST_NST: 3 / 2 LDS-DMA
-// stages at 128 (2: two blocks per CU; measured slower, 0.85 ms).
-static int list_gn(int which) {
-  const char* e = getenv(which == 0 ? "PCFM_LIST_GN_BWD" : "PCFM_LIST_GN_FWD");
-  if (e != nullptr) return atoi(e) == 128 ? 128 : 256;
-  return which == 0 ? 128 : 256;
-}
-static int list_nst() {
-  const char* e = getenv("PCFM_LIST_NST");
-  return e != nullptr && atoi(e) == 2 ? 2 : 3;
-}
+// what the masked and list forms add to a launch (unsplit launches only)
+struct SparseArgs {
+  const uint32_t* tmask = nullptr;  // conv3_occupancy_kernel's tile masks, with
+  int mmode = 0;                    //   their mode (1 forward, 2 backward-data)
+  const int* vlist = nullptr;       // the list of 2^lg-voxel runs and its
+  const int* vcount = nullptr;      //   device-side count
+  int lg = 5;
+  const uint32_t* obits = nullptr;  // bitmap of the occupied voxels (the forward list form)
+};
 
 static int igemm_cl(const void* xs, const void* wsplit, const float* bias, int b, int cin,
                     int cout, int r, float* y, void* ws, size_t ws_bytes, void* stream,
-                    const uint32_t* tmask, int mmode, const int* vlist = nullptr,
-                    const int* vcount = nullptr, int lg = 5, const uint32_t* obits = nullptr,
-                    int lgn = 256) {
+                    const Knobs& knobs, SparseArgs sa = SparseArgs{}, int list_gn = kGN) {
   PCFM_CHECK_ARG(conv3_shape_ok(b, cin, cout, r),
                  "conv3d_igemm_cl: unsupported shape b=%d cin=%d cout=%d r=%d", b, cin, cout, r);
   if (b == 0) return PCFM_OK;
-  const int V = r * r * r;
+  IgemmOptions o;
+  o.masked = sa.tmask != nullptr;
+  o.listed = sa.vlist != nullptr;
+  o.list_gn = list_gn;
+  o.slab = knobs.slab;
+  o.win = knobs.win;
+  const IgemmPlan p = plan_igemm(b, cin, cout, r, o);
+  const int V = r * r * r, S = p.S;
+  PCFM_CHECK_ARG(S == 1 || (ws != nullptr && ws_bytes >= p.ws_bytes),
+                 "conv3d_igemm_cl: workspace %zu < %zu bytes", ws_bytes, p.ws_bytes);
   const uint16_t* wh = (const uint16_t*)wsplit;
   const uint16_t* xh = (const uint16_t*)xs;
   const uint16_t* xl = xh + kSplitLo;  // interleaved hi / lo (split_off)
   hipStream_t st = (hipStream_t)stream;
-  const long long big_blocks = (long long)(V / 128) * (cout / 128) * b;
-#ifndef PCFM_CONV_NOGLDS
-  if (glds_ok(cout, r)) {
-    const int S = glds_splits(b, cin, cout, r);
-    const long long glds_blocks = (long long)(V / kGN) * (cout / kGM) * b * S;
-    const size_t need = pcfm_conv3d_igemm_cl_workspace_bytes(b, cin, cout, r);
-    PCFM_CHECK_ARG(S == 1 || (ws != nullptr && ws_bytes >= need),
-                   "conv3d_igemm_cl: workspace %zu < %zu bytes", ws_bytes, need);
-    float* part = S == 1 ? nullptr : (float*)ws;
-    const uint16_t* zrow = zero_row();  // 64 B of zeros: the padding row
-    if (zrow == nullptr) {
-      set_error("conv3d_igemm_cl: zero-row allocation failed");
-      return (int)hipErrorOutOfMemory;
-    }
-#ifndef PCFM_CONV_GK
-#define PCFM_CONV_GK 32  // 16: two blocks per CU, measured 1.15-1.18x slower
-#endif
-    // tile masks apply to unsplit launches only (a split's K range is a fixed
-    // share of all 27 taps)
-    const int mm = S == 1 && tmask != nullptr ? mmode : 0;
-    const int* vl = S == 1 ? vlist : nullptr;  // the list form is unsplit
-    const int* vc = S == 1 ? vcount : nullptr;
-    if (S == 1 && mm == 0 && vl == nullptr && cin % 64 == 0 && (r == 32 || r == 16) &&
-        conv_slab()) {  // cin % 64: an even number of 32-channel chunks (the step loop's pairs)
+  float* part = S == 1 ? nullptr : (float*)ws;
+  const uint16_t* zrow = zero_row();  // 64 B of zeros: the padding row
+  if (zrow == nullptr) {
+    set_error("conv3d_igemm_cl: zero-row allocation failed");
+    return (int)hipErrorOutOfMemory;
+  }
+  if (!p.sparse) sa = SparseArgs{};
+  const dim3 grid(p.grid), block(p.block);
+  switch (p.form) {
+    case IgemmForm::kSlab: {
       const int e = r == 32 ? allow_big_lds((const void*)conv3_igemm_slab_kernel<32>)
                             : allow_big_lds((const void*)conv3_igemm_slab_kernel<16>);
       if (e) return e;
       if (r == 32)
-        hipLaunchKernelGGL(conv3_igemm_slab_kernel<32>, dim3((unsigned)glds_blocks), dim3(512),
-                           SlabGeo<32>::LDS, st, xh, wh, zrow, bias, y, cin, cout);
+        hipLaunchKernelGGL(conv3_igemm_slab_kernel<32>, grid, block, p.lds, st, xh, wh, zrow, bias,
+                           y, cin, cout);
       else
-        hipLaunchKernelGGL(conv3_igemm_slab_kernel<16>, dim3((unsigned)glds_blocks), dim3(512),
-                           SlabGeo<16>::LDS, st, xh, wh, zrow, bias, y, cin, cout);
-      return check_launch("conv3d_igemm_cl");
+        hipLaunchKernelGGL(conv3_igemm_slab_kernel<16>, grid, block, p.lds, st, xh, wh, zrow, bias,
+                           y, cin, cout);
+      break;
     }
-    if (mm == 0 && vl == nullptr && cin % 32 == 0 && r <= 8 && win_rows(r) <= kWinRowsMax &&
-        (cin / 32) % S == 0 && conv_win()) {
-      const size_t lds = 2 * (size_t)kWinRowsMax * 64 + (size_t)kWinStages * 2 * kGM * 64;
+    case IgemmForm::kWindow: {
       const int e = allow_big_lds((const void*)conv3_igemm_win_kernel);
       if (e) return e;
-      hipLaunchKernelGGL(conv3_igemm_win_kernel, dim3((unsigned)glds_blocks), dim3(512), lds, st,
-                         xh, wh, bias, y, cin, cout, r, S, part);
-      if (S > 1) {
-        const long long total4 = (long long)b * cout * V / 4;
-        hipLaunchKernelGGL(conv3_ksum_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0,
-                           st, (const float*)part, bias, S, cout, V, total4, y);
-      }
-      return check_launch("conv3d_igemm_cl");
+      hipLaunchKernelGGL(conv3_igemm_win_kernel, grid, block, p.lds, st, xh, wh, bias, y, cin, cout,
+                         r, S, part);
+      break;
     }
-    if (vl != nullptr && cin % 32 == 0 && lgn == 128) {
-      // list form on 128-voxel tiles (list_gn): twice the blocks
-      const long long lblocks = (long long)(V / 128) * (cout / kGM) * b;
-      if (list_nst() == 2)
-        hipLaunchKernelGGL((conv3_igemm_glds_kernel<32, 128, 2>), dim3((unsigned)lblocks),
-                           dim3(256), 0, st, xh, xl, wh, wh + kSplitLo, zrow, bias, y, cin, cout,
-                           r, S, part, tmask, mm, vl, vc, lg, obits);
+    case IgemmForm::kDmaList128:
+      if (knobs.list_nst == 2)
+        hipLaunchKernelGGL((conv3_igemm_glds_kernel<128, 2>), grid, block, 0, st, xh, xl, wh,
+                           wh + kSplitLo, zrow, bias, y, cin, cout, r, S, part, sa.tmask, sa.mmode,
+                           sa.vlist, sa.vcount, sa.lg, sa.obits);
       else
-        hipLaunchKernelGGL((conv3_igemm_glds_kernel<32, 128, 3>), dim3((unsigned)lblocks),
-                           dim3(256), 0, st, xh, xl, wh, wh + kSplitLo, zrow, bias, y, cin, cout,
-                           r, S, part, tmask, mm, vl, vc, lg, obits);
-      return check_launch("conv3d_igemm_cl");
-    }
-    if (PCFM_CONV_GK == 16 || cin % 32 != 0)
-      hipLaunchKernelGGL(conv3_igemm_glds_kernel<16>, dim3((unsigned)glds_blocks), dim3(512), 0,
-                         st, xh, xl, wh, wh + kSplitLo, zrow, bias, y, cin, cout, r, S, part, tmask,
-                         mm, vl, vc, lg, S == 1 ? obits : nullptr);
-    else
-      hipLaunchKernelGGL(conv3_igemm_glds_kernel<32>, dim3((unsigned)glds_blocks), dim3(512), 0,
-                         st, xh, xl, wh, wh + kSplitLo, zrow, bias, y, cin, cout, r, S, part, tmask,
-                         mm, vl, vc, lg, S == 1 ? obits : nullptr);
-    if (S > 1) {
-      const long long total4 = (long long)b * cout * V / 4;
-      hipLaunchKernelGGL(conv3_ksum_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0,
-                         st, (const float*)part, bias, S, cout, V, total4, y);
-    }
-    return check_launch("conv3d_igemm_cl");
+        hipLaunchKernelGGL((conv3_igemm_glds_kernel<128, 3>), grid, block, 0, st, xh, xl, wh,
+                           wh + kSplitLo, zrow, bias, y, cin, cout, r, S, part, sa.tmask, sa.mmode,
+                           sa.vlist, sa.vcount, sa.lg, sa.obits);
+      break;
+    case IgemmForm::kDma:
+      hipLaunchKernelGGL(conv3_igemm_glds_kernel<>, grid, block, 0, st, xh, xl, wh, wh + kSplitLo,
+                         zrow, bias, y, cin, cout, r, S, part, sa.tmask, sa.mmode, sa.vlist,
+                         sa.vcount, sa.lg, sa.obits);
+      break;
   }
-#endif
-  if (big_blocks >= 2 * kCUs) {
-    hipLaunchKernelGGL((conv3_igemm_cl_kernel<128, 128, PCFM_CONV_KT>),
-                       dim3((V / 128) * (cout / 128) * b), dim3(256), 0, st, xh, xl, wh, wh + kSplitLo,
-                       bias, y, cin, cout, r, 1, nullptr);
-  } else {
-    const int S = igemm_splits(b, cin, cout, r);
-    const size_t need = pcfm_conv3d_igemm_cl_workspace_bytes(b, cin, cout, r);
-    PCFM_CHECK_ARG(S == 1 || (ws != nullptr && ws_bytes >= need),
-                   "conv3d_igemm_cl: workspace %zu < %zu bytes", ws_bytes, need);
-    const int items = (V / 64) * (cout / 64) * b;
-    hipLaunchKernelGGL((conv3_igemm_cl_kernel<64, 64, PCFM_CONV_KT>), dim3(items * S), dim3(256),
-                       0, st, xh, xl, wh, wh + kSplitLo, bias, y, cin, cout, r, S, (float*)ws);
-    if (S > 1) {
-      const long long total4 = (long long)b * cout * V / 4;
-      hipLaunchKernelGGL(conv3_ksum_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0,
-                         st, (const float*)ws, bias, S, cout, V, total4, y);
-    }
-  }
+  if (S > 1) launch_ksum(part, bias, S, b, cout, V, y, st);
   return check_launch("conv3d_igemm_cl");
 }
 
 extern "C" int pcfm_conv3d_igemm_cl(const void* xs, const void* wsplit, const float* bias, int b,
                                     int cin, int cout, int r, float* y, void* ws,
                                     size_t ws_bytes, void* stream) {
-  return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream, nullptr, 0);
+  return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream, read_knobs());
 }
 
 extern "C" int pcfm_conv3d_igemm_cl_occ(const void* xs, const void* wsplit, const float* bias,
@@ -2270,14 +2042,16 @@ extern "C" int pcfm_conv3d_igemm_cl_occ(const void* xs, const void* wsplit, cons
   PCFM_CHECK_ARG(tmask != nullptr && (mode == 1 || mode == 2) && (r * r * r) % 256 == 0,
                  "conv3d_igemm_cl_occ: need a tile mask, mode 1 or 2 and r^3 %% 256 == 0 "
                  "(mode=%d r=%d)", mode, r);
-  return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream,
-                  (const uint32_t*)tmask, mode);
+  SparseArgs sa;
+  sa.tmask = (const uint32_t*)tmask;
+  sa.mmode = mode;
+  return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream, read_knobs(), sa);
 }
 
 extern "C" size_t pcfm_conv3d_occupancy_bytes(int b, int r) {
   const long long v = (long long)r * r * r;
   if (b <= 0 || r <= 0 || v % 256 != 0) return 0;
-  return (size_t)b * (v / 256 + v / 64 + v / 16) * sizeof(uint32_t);
+  return OccLayout(b, r).total * sizeof(uint32_t);
 }
 
 extern "C" int pcfm_conv3d_occupancy(const int* cnt, int b, int r, unsigned* masks,
@@ -2285,54 +2059,38 @@ extern "C" int pcfm_conv3d_occupancy(const int* cnt, int b, int r, unsigned* mas
   PCFM_CHECK_ARG(pcfm_conv3d_occupancy_bytes(b, r) > 0,
                  "conv3d_occupancy: bad shape b=%d r=%d (r^3 %% 256 == 0)", b, r);
   const int V = r * r * r;
+  const OccLayout L(b, r);
+  uint32_t* m = (uint32_t*)masks;
   hipLaunchKernelGGL(conv3_occupancy_kernel, dim3(V / 256, b), dim3(256), 0, (hipStream_t)stream,
-                     cnt, r, (uint32_t*)masks, (uint32_t*)masks + (size_t)b * (V / 256),
-                     (uint32_t*)masks + (size_t)b * (V / 256 + V / 64));
+                     cnt, r, m + L.tmask, m + L.cmask, m + L.kmask);
   return check_launch("conv3d_occupancy");
 }
 
-// Buffer: int32 counts[4] | pad to 64 | per-tile counts / offsets [2][tiles] |
-// list 0 [B V / 32] | list 1 [B V / 32] | per-tile counts / offsets of lists 2, 3
-// [2][tiles] | list 2 [B V] (the occupied voxels, global indices b V + v) |
-// list 3 [B V] (the voxels with an occupied voxel in their 3x3x3 neighbourhood)
-// | bitmaps of lists 2, 3 [2][B V / 32] (bit v & 31 of word v >> 5).
 extern "C" size_t pcfm_conv3d_vlist_bytes(int b, int r) {
   const long long v = (long long)r * r * r;
   if (b <= 0 || r <= 0 || v % 256 != 0 || (long long)b * v >= (1LL << 31)) return 0;
-  const long long tiles = (long long)b * v / 256;
-  return (size_t)(64 + 4 * tiles + 4 * (long long)b * v / kChunk + 2 * (long long)b * v) *
-         sizeof(int);
+  return VlistLayout(b, r).total * sizeof(int);
 }
 
 extern "C" int pcfm_conv3d_vlist(const int* cnt, int b, int r, int* lists, void* stream) {
   PCFM_CHECK_ARG(pcfm_conv3d_vlist_bytes(b, r) > 0,
                  "conv3d_vlist: bad shape b=%d r=%d (r^3 %% 256 == 0, b r^3 < 2^31)", b, r);
-  const int V = r * r * r, tiles = b * (V / 256);
+  const VlistLayout L(b, r);
+  const int tiles = (int)L.tiles;
   hipStream_t st = (hipStream_t)stream;
-  int* tc = lists + 64;
-  int* l0 = tc + 2 * tiles;
-  int* tc2 = l0 + 2 * ((size_t)b * V / kChunk);
-  int* l2 = tc2 + 2 * tiles;
+  int* tc = lists + L.tcount;
+  int* tc2 = lists + L.tcount2;
   hipLaunchKernelGGL(conv3_vlist_count_kernel, dim3(tiles), dim3(256), 0, st, cnt, r, tiles, tc,
                      tc2);
-  hipLaunchKernelGGL(conv3_vlist_scan_kernel, dim3(1), dim3(1024), 0, st, tc, tiles, lists, 2);
-  hipLaunchKernelGGL(conv3_vlist_scan_kernel, dim3(1), dim3(1024), 0, st, tc2, tiles, lists + 2,
-                     2);
-  uint32_t* bits = (uint32_t*)(l2 + 2 * (size_t)b * V);
+  hipLaunchKernelGGL(conv3_vlist_scan_kernel, dim3(1), dim3(1024), 0, st, tc, tiles,
+                     lists + L.counts, 2);
+  hipLaunchKernelGGL(conv3_vlist_scan_kernel, dim3(1), dim3(1024), 0, st, tc2, tiles,
+                     lists + L.counts + 2, 2);
   hipLaunchKernelGGL(conv3_vlist_write_kernel, dim3(tiles), dim3(256), 0, st, cnt, r, tiles, tc,
-                     l0, l0 + (size_t)b * V / kChunk, (const int*)tc2, l2, l2 + (size_t)b * V,
-                     bits, bits + (size_t)b * V / kChunk);
+                     lists + L.list[0], lists + L.list[1], (const int*)tc2, lists + L.list[2],
+                     lists + L.list[3], (uint32_t*)(lists + L.bits[0]),
+                     (uint32_t*)(lists + L.bits[1]));
   return check_launch("conv3d_vlist");
-}
-
-// The list forms over single voxels (lists 2 / 3) instead of 32-voxel chunks
-// (lists 0 / 1): env PCFM_LIST_VOX bit 0 = backward-data (which 0), bit 1 =
-// forward (which 1); default 3; read per call (A/B runs).  At the C2 stages an
-// occupied chunk holds 27 % (r = 32) / 36 % (r = 16) occupied voxels, and a
-// listed forward chunk 49 % / 61 % active voxels.
-static int list_vox() {
-  const char* e = getenv("PCFM_LIST_VOX");
-  return e == nullptr ? 3 : (atoi(e) & 3);
 }
 
 extern "C" int pcfm_conv3d_igemm_cl_list(const void* xs, const void* wsplit, const float* bias,
@@ -2346,87 +2104,63 @@ extern "C" int pcfm_conv3d_igemm_cl_list(const void* xs, const void* wsplit, con
   PCFM_CHECK_ARG(conv3_shape_ok(b, cin, cout, r),
                  "conv3d_igemm_cl_list: unsupported shape b=%d cin=%d cout=%d r=%d", b, cin, cout,
                  r);
-  const int V = r * r * r, tiles = b * (V / 256);
-#ifndef PCFM_CONV_NOGLDS
-  const bool listed = glds_ok(cout, r) && glds_splits(b, cin, cout, r) == 1;
-#else
-  const bool listed = false;
-#endif
-  if (!listed)  // no list form for this shape: the dense GEMM (every voxel)
-    return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream, nullptr, 0);
-  const bool vox = (list_vox() >> which) & 1;
-  const int* l = vox ? lists + 64 + 4 * tiles + 2 * ((size_t)b * V / kChunk) +
-                           (size_t)which * b * V
-                     : lists + 64 + 2 * tiles + (size_t)which * b * V / kChunk;
-  hipStream_t st = (hipStream_t)stream;
-  const uint32_t* vbits =
-      vox ? (const uint32_t*)(lists + 64 + 4 * tiles + 2 * ((size_t)b * V / kChunk) +
-                              2 * (size_t)b * V) +
-                (size_t)which * b * V / kChunk
-          : nullptr;
-  hipLaunchKernelGGL(conv3_fill_unlisted_kernel, dim3(tiles), dim3(256), 0, st, cnt, r, cout,
-                     which, bias, y, vbits);
+  const Knobs knobs = read_knobs();
+  if (plan_igemm(b, cin, cout, r, IgemmOptions{}).S != 1)  // no list form for a split shape:
+    return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream, knobs);  // dense
+  const VlistLayout L(b, r);
+  // over single voxels (lists 2 / 3) or 32-voxel chunks (lists 0 / 1)
+  const bool vox = (knobs.list_vox >> which) & 1;
+  const int li = (vox ? 2 : 0) + which;
+  SparseArgs sa;
+  sa.vlist = lists + L.list[li];
+  sa.vcount = lists + L.counts + li;
+  sa.lg = vox ? 0 : 5;
+  // the forward reads occupied neighbour rows only (list 2's bitmap)
+  if (which == 1 && knobs.list_zrow) sa.obits = (const uint32_t*)(lists + L.bits[0]);
+  const uint32_t* vbits = vox ? (const uint32_t*)(lists + L.bits[which]) : nullptr;
+  hipLaunchKernelGGL(conv3_fill_unlisted_kernel, dim3((unsigned)L.tiles), dim3(256), 0,
+                     (hipStream_t)stream, cnt, r, cout, which, bias, y, vbits);
   const int e = check_launch("conv3d_igemm_cl_list");
   if (e) return e;
-  // the forward reads occupied neighbour rows only (list 2's bitmap; env
-  // PCFM_LIST_ZROW=0: every in-volume row, A/B)
-  const char* zr = getenv("PCFM_LIST_ZROW");
-  const uint32_t* obits =
-      which == 1 && (zr == nullptr || zr[0] != '0')
-          ? (const uint32_t*)(lists + 64 + 4 * tiles + 2 * ((size_t)b * V / kChunk) +
-                              2 * (size_t)b * V)
-          : nullptr;
-  return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream, nullptr, 0, l,
-                  vox ? lists + 2 + which : lists + which, vox ? 0 : 5, obits,
-                  vox ? list_gn(which) : 256);
-}
-
-static int wgrad_cap(int b, int r, int S) {
-  const long long nchunk = (long long)b * r * r * r / kWV;
-  return (int)((nchunk + S - 1) / S);
+  return igemm_cl(xs, wsplit, bias, b, cin, cout, r, y, ws, ws_bytes, stream, knobs, sa,
+                  vox ? knobs.list_gn[which] : kGN);
 }
 
 static int wgrad_cl(const void* xs, const void* gys, int b, int cin, int cout, int r,
                     const uint32_t* cmask, float* grad_w, void* ws, size_t ws_bytes,
                     void* stream, const uint32_t* kmask = nullptr) {
-  PCFM_CHECK_ARG(b > 0 && conv3_shape_ok(b, cin, cout, r) && cin % kMT == 0,
+  PCFM_CHECK_ARG(wgrad_shape_ok(b, cin, cout, r),
                  "conv3d_wgrad_cl: unsupported shape b=%d cin=%d cout=%d r=%d", b, cin, cout, r);
-  const size_t need = wgrad_partial_bytes(b, cin, cout, r);
+  const WgradPlan p = plan_wgrad(b, cin, cout, r);
+  const size_t need = p.part_bytes;
   PCFM_CHECK_ARG(ws_bytes >= need, "conv3d_wgrad_cl: workspace %zu < %zu bytes", ws_bytes, need);
-  const int S = conv3_wgrad_splits(b, cin, cout, r);
-  const int V = r * r * r;
+  const int S = p.S, V = r * r * r;
   hipStream_t st = (hipStream_t)stream;
-  const int tiles = 27 * (cout / kMT) * (cin / kMT);
   const uint16_t* xh = (const uint16_t*)xs;
   const uint16_t* gh = (const uint16_t*)gys;
-  if (conv3_wgrad3_ok(r)) {
+  if (p.three) {
     const int e = allow_big_lds((const void*)conv3_wgrad3_kernel);
     if (e) return e;
     int* lists = nullptr;
     int* counts = nullptr;
-    const int cap = wgrad_cap(b, r, S);
     // decided before anything is launched: the K-slice masks of a split's chunks
-    // are staged in LDS behind the two buffers; where they do not fit the kernel
-    // runs without them (the skip only drops exact-zero products)
-    if (kmask != nullptr && 2 * (size_t)kW3Buf + (size_t)cap * 16 > (size_t)kLdsBytesMax)
-      kmask = nullptr;
+    // are staged in LDS behind the two buffers (WgradPlan::kmask_fits)
+    if (!p.kmask_fits) kmask = nullptr;
     if (cmask != nullptr) {
-      const size_t lb = (size_t)9 * S * cap * sizeof(int), cb = (size_t)9 * S * sizeof(int);
-      PCFM_CHECK_ARG(ws_bytes >= need + lb + cb,
-                     "conv3d_wgrad_cl_occ: workspace %zu < %zu bytes", ws_bytes, need + lb + cb);
+      PCFM_CHECK_ARG(ws_bytes >= need + p.list_bytes + p.count_bytes,
+                     "conv3d_wgrad_cl_occ: workspace %zu < %zu bytes", ws_bytes,
+                     need + p.list_bytes + p.count_bytes);
       lists = (int*)((char*)ws + need);
-      counts = (int*)((char*)ws + need + lb);
+      counts = (int*)((char*)ws + need + p.list_bytes);
       hipLaunchKernelGGL(conv3_wgrad_lists_kernel, dim3(9, S), dim3(64), 0, st, cmask,
-                         b * (V / kWV), S, cap, lists, counts);
+                         b * (V / kWV), S, p.cap, lists, counts);
     }
-    const size_t lds = 2 * (size_t)kW3Buf + (kmask != nullptr ? (size_t)cap * 16 : 0);
-    hipLaunchKernelGGL(conv3_wgrad3_kernel, dim3(tiles / 3 * S), dim3(kW3Threads), lds, st,
-                       xh, xh + kSplitLo, gh, gh + kSplitLo, b, cin, cout, r,
-                       S, (float*)ws, lists, counts, cap, kmask);
+    hipLaunchKernelGGL(conv3_wgrad3_kernel, dim3(p.grid), dim3(p.block),
+                       kmask != nullptr ? p.lds_kmask : p.lds, st, xh, xh + kSplitLo, gh,
+                       gh + kSplitLo, b, cin, cout, r, S, (float*)ws, lists, counts, p.cap, kmask);
   } else {
-    hipLaunchKernelGGL(conv3_wgrad_cl_kernel, dim3(tiles * S), dim3(256), 0, st, xh,
-                       xh + kSplitLo, gh, gh + kSplitLo, b, cin, cout, r, S,
-                       (float*)ws);
+    hipLaunchKernelGGL(conv3_wgrad_cl_kernel, dim3(p.grid), dim3(p.block), 0, st, xh,
+                       xh + kSplitLo, gh, gh + kSplitLo, b, cin, cout, r, S, (float*)ws);
   }
   hipLaunchKernelGGL(conv3_wgrad_reduce_kernel, dim3(ceil_div((long long)cout * cin, 64)),
                      dim3(256), 0, st, (const float*)ws, cout, cin, S, grad_w);
@@ -2440,10 +2174,9 @@ extern "C" int pcfm_conv3d_wgrad_cl(const void* xs, const void* gys, int b, int 
 }
 
 extern "C" size_t pcfm_conv3d_wgrad_occ_workspace_bytes(int b, int cin, int cout, int r) {
-  if (b <= 0 || !conv3_shape_ok(b, cin, cout, r) || cin % kMT != 0) return 0;
-  const int S = conv3_wgrad_splits(b, cin, cout, r);
-  return wgrad_partial_bytes(b, cin, cout, r) +
-         (size_t)9 * S * (wgrad_cap(b, r, S) + 1) * sizeof(int);
+  if (!wgrad_shape_ok(b, cin, cout, r)) return 0;
+  const WgradPlan p = plan_wgrad(b, cin, cout, r);
+  return p.part_bytes + p.list_bytes + p.count_bytes;
 }
 
 extern "C" int pcfm_conv3d_wgrad_cl_occ(const void* xs, const void* gys, int b, int cin,
@@ -2451,11 +2184,8 @@ extern "C" int pcfm_conv3d_wgrad_cl_occ(const void* xs, const void* gys, int b, 
                                         void* ws, size_t ws_bytes, void* stream) {
   PCFM_CHECK_ARG(masks != nullptr && (r * r * r) % 256 == 0,
                  "conv3d_wgrad_cl_occ: need the occupancy masks and r^3 %% 256 == 0 (r=%d)", r);
-  const int V = r * r * r;
-  // the chunk masks follow the tile masks in pcfm_conv3d_occupancy's buffer
-  const uint32_t* cmask = (const uint32_t*)masks + (size_t)b * (V / 256);
-  // the K-slice masks follow the chunk masks (PCFM_WGRAD_KSKIP=0: none, A/B knob)
-  const char* ks = std::getenv("PCFM_WGRAD_KSKIP");
-  const uint32_t* kmask = (ks != nullptr && ks[0] == '0') ? nullptr : cmask + (size_t)b * (V / 64);
-  return wgrad_cl(xs, gys, b, cin, cout, r, cmask, grad_w, ws, ws_bytes, stream, kmask);
+  const OccLayout L(b, r);
+  const uint32_t* m = (const uint32_t*)masks;
+  return wgrad_cl(xs, gys, b, cin, cout, r, m + L.cmask, grad_w, ws, ws_bytes, stream,
+                  read_knobs().wgrad_kskip ? m + L.kmask : nullptr);
 }

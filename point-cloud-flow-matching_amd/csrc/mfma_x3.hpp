@@ -88,6 +88,50 @@ __device__ __forceinline__ void tile_mfma(const uint16_t* buf, int wr, int wc, i
   }
 }
 
+// The three-term product of one 16-deep K-slice in PRODUCT-MAJOR order (all
+// ah*bh, then all ah*bl, then all al*bh): consecutive MFMAs write different
+// accumulators.  The voxel convolution's order; tile_mfma above interleaves
+// the three terms per accumulator and is pointwise.hip's.
+template <int SI, int SJ>
+__device__ __forceinline__ void mfma_x3(const bf16x8 (&ah)[SI], const bf16x8 (&al)[SI],
+                                        const bf16x8 (&bh)[SJ], const bf16x8 (&bl)[SJ],
+                                        f32x16 (&acc)[SI][SJ]) {
+#pragma unroll
+  for (int i = 0; i < SI; ++i)
+#pragma unroll
+    for (int j = 0; j < SJ; ++j)
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < SI; ++i)
+#pragma unroll
+    for (int j = 0; j < SJ; ++j)
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+#pragma unroll
+  for (int i = 0; i < SI; ++i)
+#pragma unroll
+    for (int j = 0; j < SJ; ++j)
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+}
+
+template <int SI, int SJ>
+__device__ __forceinline__ void zero_acc(f32x16 (&acc)[SI][SJ]) {
+#pragma unroll
+  for (int i = 0; i < SI; ++i)
+#pragma unroll
+    for (int j = 0; j < SJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+}
+
+// A 1-D grid's block id dealt to the 8 XCDs in contiguous runs (T1 remap):
+// hardware sends block i to XCD i % 8; the id returned makes each XCD sweep one
+// contiguous eighth of [0, nwg), so concurrently resident blocks share rows in
+// their XCD's L2 instead of streaming them from the Infinity Cache.
+__device__ __forceinline__ int xcd_deal(int id, int nwg) {
+  const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
+}
+
 // split N consecutive fp32 (same LDS row) into the hi and lo images.  The
 // (__bf16) casts round to nearest even and lower to gfx950's packed
 // v_cvt_pk_bf16_f32 (one instruction per pair), hi is widened back exactly.

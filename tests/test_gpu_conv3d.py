@@ -108,12 +108,14 @@ def test_voxel_conv_module_matches_conv3d(ops):
 
 
 @pytest.mark.parametrize("b,cin,cout,r", [(2, 128, 128, 32), (2, 256, 256, 16), (1, 128, 256, 16),
-                                          (1, 256, 128, 32)])
+                                          (1, 256, 128, 32), (5, 128, 256, 16)])
 def test_slab_form_is_bit_identical(ops, monkeypatch, b, cin, cout, r):
     """The slab form of the dense r = 32 / 16 GEMM (conv3_igemm_slab_kernel: B from a
     per-(chunk, dx) 2-D slab in LDS) runs the LDS-DMA kernel's K-steps in the same
     order with the same operands: forward and backward-data outputs bit-identical,
-    including the volume's border voxels (zero rows of the slab)."""
+    including the volume's border voxels (zero rows of the slab).  A launch takes the
+    slab form only where it is unsplit (test_added_cases_reach_their_forms): the
+    forward of (5, 128, 256, 16) is the r = 16 case that does."""
     g = torch.Generator(device="cuda").manual_seed(7 * r + cin)
     x = torch.randn(b, cin, r, r, r, device="cuda", generator=g)
     w = torch.randn(cout, cin, 3, 3, 3, device="cuda", generator=g) / (27 * cin) ** 0.5
@@ -133,28 +135,31 @@ def test_slab_form_is_bit_identical(ops, monkeypatch, b, cin, cout, r):
     assert _rel(out["1"][0], y64) < TOL
 
 
-@pytest.mark.parametrize("r", [16, 32])
-def test_slab_form_padding_counts(ops, r):
+@pytest.mark.parametrize("b,c,r", [pytest.param(1, 128, 16, id="16"), pytest.param(1, 128, 32, id="32"),
+                                   pytest.param(5, 256, 16, id="16-b5-c256")])
+def test_slab_form_padding_counts(ops, b, c, r):
     """All-ones input and kernel at the slab form's resolutions: every output is the
-    number of in-grid neighbours times C (zero rows at all six faces)."""
-    c = 128
-    x = torch.ones(1, c, r, r, r, device="cuda")
+    number of in-grid neighbours times C (zero rows at all six faces).  b = 5, c = 256
+    is the r = 16 case that is unsplit, i.e. that reaches the slab kernel."""
+    x = torch.ones(b, c, r, r, r, device="cuda")
     w = torch.ones(c, c, 3, 3, 3, device="cuda")
     y = ops.conv3d_forward(x, w, None)
     idx = torch.arange(r, device="cuda")
     n1 = 3 - (idx == 0).int() - (idx == r - 1).int()
     cnt = (n1[:, None, None] * n1[None, :, None] * n1[None, None, :]).float() * c
-    assert torch.equal(y[0, 0], cnt) and torch.equal(y[0, c - 1], cnt)
+    assert torch.equal(y[0, 0], cnt) and torch.equal(y[b - 1, c - 1], cnt)
 
 
 @pytest.mark.parametrize("b,cin,cout,r", [(8, 256, 256, 8), (2, 256, 128, 8), (4, 128, 256, 8),
-                                          (3, 128, 128, 8)])
+                                          (3, 128, 128, 8), (2, 256, 256, 8)])
 def test_window_form_is_bit_identical(ops, monkeypatch, b, cin, cout, r):
     """The window form of the small-grid split-K GEMM (conv3_igemm_win_kernel: B
     for all 27 taps from one staged window of the input per 32-channel chunk) runs
     the LDS-DMA kernel's K-steps in the same order with the same operands (zeroed
     fragments where that kernel reads its zero row): forward and backward-data
-    outputs bit-identical, incl. the border voxels, and the fp64 pin."""
+    outputs bit-identical, incl. the border voxels, and the fp64 pin.  The window form
+    needs whole 32-channel chunks per split: (2, 256, 256, 8) has eight chunks over
+    eight splits in both directions (test_added_cases_reach_their_forms)."""
     g = torch.Generator(device="cuda").manual_seed(11 * r + cin + cout)
     x = torch.randn(b, cin, r, r, r, device="cuda", generator=g)
     w = torch.randn(cout, cin, 3, 3, 3, device="cuda", generator=g) / (27 * cin) ** 0.5
@@ -186,3 +191,21 @@ def test_window_form_padding_counts(ops):
     cnt = (n1[:, None, None] * n1[None, :, None] * n1[None, None, :]).float() * c
     assert torch.equal(y[0, 0], cnt) and torch.equal(y[1, c - 1], cnt)
 
+
+
+def test_added_cases_reach_their_forms(ops):
+    """The workspace query tells the split count (1 byte: unsplit, else splits x output
+    bytes), which decides the form: the slab form runs unsplit launches at r = 32 / 16,
+    the window form split-K launches at r = 8 whose K / 32 chunks divide by the splits.
+    Pins the cases added to the tests above to the kernels they are there for."""
+    from pcfm import _lib
+
+    def splits(b, cin, cout, r):
+        n = _lib.query("pcfm_conv3d_igemm_cl_workspace_bytes", b, cin, cout, r)
+        return 1 if n == 1 else n // (4 * b * cout * r ** 3)
+
+    assert splits(5, 128, 256, 16) == 1      # slab<16>, forward
+    assert splits(5, 256, 256, 16) == 1      # slab<16>, the padding counts
+    assert splits(2, 128, 128, 32) == 1      # slab<32>
+    assert splits(2, 256, 256, 8) == 8 and (256 // 32) % 8 == 0   # window, both directions
+    assert splits(3, 128, 128, 8) == 8 and (128 // 32) % 8 != 0   # split, never the window

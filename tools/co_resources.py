@@ -51,7 +51,7 @@ def main():
     table = rows(lib, {
         "pw_gemm256 (aggressor: corrupts)": lambda n: "pw_gemm256_kernel" in n,
         "conv3_wgrad3 (aggressor: corrupts)": lambda n: "conv3_wgrad3_kernel" in n,
-        "conv3_igemm_glds<32,256,3> (clean)": lambda n: "conv3_igemm_glds_kernelILi32ELi256" in n,
+        "conv3_igemm_glds<256,3> (clean)": lambda n: "conv3_igemm_glds_kernelILi256ELi3" in n,
         "gather_rows4<ProvDevox> (victim, R16/R8)": lambda n: "gather_rows4_kernelINS_9ProvDevox" in n,
         "gather_rows1<ProvDevox,2> (victim, R32)": lambda n: "gather_rows1_kernelINS_9ProvDevoxELi2" in n,
     }, dyn_lds={"conv3_wgrad3 (aggressor: corrupts)": 2 * (2 * 64 * 256 + 2 * 68 * 256),
