@@ -54,44 +54,65 @@ struct Tile {
   static constexpr int BUF = 2 * A_ELEMS + 2 * B_ELEMS;
 };
 
+// The three-term product of one 16-deep K-slice in PER-ACCUMULATOR order (the
+// three terms of an accumulator back to back), from fragments in registers.
+// pointwise.hip's order; mfma_x3 below is the voxel convolution's.
+template <int SI, int SJ>
+__device__ __forceinline__ void mfma_x3_interleaved(const bf16x8 (&ah)[SI], const bf16x8 (&al)[SI],
+                                                    const bf16x8 (&bh)[SJ], const bf16x8 (&bl)[SJ],
+                                                    f32x16 (&acc)[SI][SJ]) {
+#pragma unroll
+  for (int i = 0; i < SI; ++i)
+#pragma unroll
+    for (int j = 0; j < SJ; ++j) {
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
+    }
+}
+
+// the hi and lo fragment of one LDS row pair: 8 bf16 at element offset o
+__device__ __forceinline__ void lds_frag(const uint16_t* hi, const uint16_t* lo, int o, bf16x8& fh,
+                                         bf16x8& fl) {
+  fh = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(hi + o));
+  fl = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(lo + o));
+}
+
+// One K-step (kKT deep) of a wave's SI x SJ accumulators from LDS images of
+// `ld`-strided bf16 rows: lane (r, h) reads rows arow + 32 i of the A pair and
+// brow + 32 j of the B pair (arow / brow include the lane's r).
+template <int SI, int SJ>
+__device__ __forceinline__ void lds_mfma_x3(const uint16_t* sAh, const uint16_t* sAl, int arow,
+                                            const uint16_t* sBh, const uint16_t* sBl, int brow,
+                                            int ld, int h, f32x16 (&acc)[SI][SJ]) {
+#pragma unroll
+  for (int kk = 0; kk < kKT / 16; ++kk) {
+    bf16x8 ah[SI], al[SI], bh[SJ], bl[SJ];
+#pragma unroll
+    for (int i = 0; i < SI; ++i)
+      lds_frag(sAh, sAl, (arow + i * 32) * ld + kk * 16 + 8 * h, ah[i], al[i]);
+#pragma unroll
+    for (int j = 0; j < SJ; ++j)
+      lds_frag(sBh, sBl, (brow + j * 32) * ld + kk * 16 + 8 * h, bh[j], bl[j]);
+    mfma_x3_interleaved(ah, al, bh, bl, acc);
+  }
+}
+
+// The 2 x 2-wave block's K-step on one Tile<TM, TN> buffer (Ah | Al | Bh | Bl).
 template <int TM, int TN>
 __device__ __forceinline__ void tile_mfma(const uint16_t* buf, int wr, int wc, int r, int h,
                                           f32x16 (&acc)[TM / 64][TN / 64]) {
   using T = Tile<TM, TN>;
-  const uint16_t* sAh = buf;
-  const uint16_t* sAl = buf + T::A_ELEMS;
   const uint16_t* sBh = buf + 2 * T::A_ELEMS;
-  const uint16_t* sBl = sBh + T::B_ELEMS;
-#pragma unroll
-  for (int kk = 0; kk < kKT / 16; ++kk) {
-    bf16x8 ah[T::SI], al[T::SI], bh[T::SJ], bl[T::SJ];
-#pragma unroll
-    for (int i = 0; i < T::SI; ++i) {
-      const int o = (wr * (TM / 2) + i * 32 + r) * kLDR + kk * 16 + 8 * h;
-      ah[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sAh + o));
-      al[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sAl + o));
-    }
-#pragma unroll
-    for (int j = 0; j < T::SJ; ++j) {
-      const int o = (wc * (TN / 2) + j * 32 + r) * kLDR + kk * 16 + 8 * h;
-      bh[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sBh + o));
-      bl[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sBl + o));
-    }
-#pragma unroll
-    for (int i = 0; i < T::SI; ++i)
-#pragma unroll
-      for (int j = 0; j < T::SJ; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-      }
-  }
+  lds_mfma_x3(buf, buf + T::A_ELEMS, wr * (TM / 2) + r, sBh, sBh + T::B_ELEMS, wc * (TN / 2) + r,
+              kLDR, h, acc);
 }
 
 // The three-term product of one 16-deep K-slice in PRODUCT-MAJOR order (all
 // ah*bh, then all ah*bl, then all al*bh): consecutive MFMAs write different
-// accumulators.  The voxel convolution's order; tile_mfma above interleaves
-// the three terms per accumulator and is pointwise.hip's.
+// accumulators.  The voxel convolution's order; mfma_x3_interleaved above is
+// pointwise.hip's.  Within one accumulator the order of the three terms is the
+// same, so the two give the same sums.
 template <int SI, int SJ>
 __device__ __forceinline__ void mfma_x3(const bf16x8 (&ah)[SI], const bf16x8 (&al)[SI],
                                         const bf16x8 (&bh)[SJ], const bf16x8 (&bl)[SJ],
@@ -200,8 +221,15 @@ __device__ __forceinline__ bf16x8 tr_operand(const uint8_t* img, int kk, int col
 }
 
 // ---------------------------------------------------------------------------
+// The accumulator row map of v_mfma_f32_32x32x16: element e (0..15) of lane
+// half h (lane >> 5) is row acc_row(e, h) of the 32x32 block; the lane's low
+// five bits are its column.
+__device__ __forceinline__ constexpr int acc_row(int e, int h) {
+  return (e & 3) + 8 * (e >> 2) + 4 * h;
+}
+
 // Epilogue bias of one 32x32 accumulator: element e of lane half h is row
-// mg + (e & 3) + 8 (e >> 2) + 4 h.  All 16 values are loaded before the
+// mg + acc_row(e, h).  All 16 values are loaded before the
 // tile's first store: vmcnt counts stores too, so a bias load placed after
 // a store waits for that store's acknowledgement -- 16-64 serialised round
 // trips per wave in the fused-add form.  Rows >= M read row M - 1 (unused).
@@ -210,7 +238,12 @@ __device__ __forceinline__ void load_bias16(const float* __restrict__ bias, int 
                                             float (&bv)[16]) {
 #pragma unroll
   for (int e = 0; e < 16; ++e)
-    bv[e] = bias != nullptr ? bias[min(mg + (e & 3) + 8 * (e >> 2) + 4 * h, M - 1)] : 0.0f;
+    bv[e] = bias != nullptr ? bias[min(mg + acc_row(e, h), M - 1)] : 0.0f;
+}
+// the same from an LDS image of the tile's bias rows (row 0 = the tile's first)
+__device__ __forceinline__ void lds_bias16(const float* sbias, int row, int h, float (&bv)[16]) {
+#pragma unroll
+  for (int e = 0; e < 16; ++e) bv[e] = sbias[row + acc_row(e, h)];
 }
 
 }  // namespace

@@ -20,13 +20,8 @@ inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
 // GEMM output stores are streamed (non-temporal): the outputs (80-330 MB) do
 // not fit L2 and are next read by another kernel.  256 -> 256 at N = 20000:
 // forward 112 -> 106 us, backward-data 134 -> 116 us (tools/pw_ab.py)
-__device__ __forceinline__ void out_store(float* p, float v) {
-#ifndef PCFM_PW_CACHED_STORE
-  nt_st(v, p);
-#else
-  *p = v;
-#endif
-}
+__device__ __forceinline__ void out_store(float* p, float v) { nt_st(v, p); }
+
 // rows of the weight image: above 256 a multiple of 256, so the 256-row tile
 // (x read once per 256 output rows) applies -- ContextNet head_pre's backward-data
 // (M = 640 -> 768: x read 3 times instead of 5 by 128-row tiles)
@@ -121,10 +116,10 @@ __global__ void __launch_bounds__(256)
       rmask |= ok ? 0u : (1u << q);
     }
   };
-  auto store = [&](uint16_t* buf) {
+  auto store = [&]() {
     if (astage) {
-      uint16_t* dh = buf + arow * kLDR + ahalf;
-      uint16_t* dl = buf + T::A_ELEMS + arow * kLDR + ahalf;
+      uint16_t* dh = lds + arow * kLDR + ahalf;
+      uint16_t* dl = lds + T::A_ELEMS + arow * kLDR + ahalf;
       *reinterpret_cast<uint4*>(dh) = ra0;
       *reinterpret_cast<uint4*>(dh + 8) = ra1;
       *reinterpret_cast<uint4*>(dl) = ra2;
@@ -132,26 +127,21 @@ __global__ void __launch_bounds__(256)
     }
 #pragma unroll
     for (int q = 0; q < CPT; ++q) rb[q] = (rmask >> q) & 1u ? 0.0f : rb[q];
-    uint16_t* bh = buf + 2 * T::A_ELEMS + sp * kLDR + ch;
+    uint16_t* bh = lds + 2 * T::A_ELEMS + sp * kLDR + ch;
     store_split<CPT>(rb, bh, bh + T::B_ELEMS);
   };
 
   f32x16 acc[T::SI][T::SJ];
-#pragma unroll
-  for (int i = 0; i < T::SI; ++i)
-#pragma unroll
-    for (int j = 0; j < T::SJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+  zero_acc(acc);
 
   load(0);
-  store(lds);
+  store();
   __syncthreads();
   for (int s = 0; s < nsteps; ++s) {
     if (s + 1 < nsteps) load(s + 1);
     tile_mfma<TM, TN>(lds, wr, wc, r, h, acc);
     __syncthreads();
-    if (s + 1 < nsteps) store(lds);
+    if (s + 1 < nsteps) store();
     __syncthreads();
   }
   const int bo = b * bias_bstride;  // per-cloud bias row (0: one shared bias)
@@ -166,7 +156,7 @@ __global__ void __launch_bounds__(256)
     for (int j = 0; j < T::SJ; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int dm = (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int dm = acc_row(e, h);
         const int m = mg + dm;
         const int p = p0 + wc * (TN / 2) + j * 32 + r;
         if (m < M && p < N) out_store(yr + (size_t)dm * N + p, acc[i][j][e] + bv[e]);
@@ -204,6 +194,51 @@ __device__ __forceinline__ void xpose_reduce_stage(float* v, bool upper) {
   }
 }
 
+// The BatchNorm statistics of one 32-row group over one group of 32 NA points
+// (the NA accumulators of row i side by side, from point g0 on; lane r holds points
+// g0 + 32 j + r): per row the mean and centred sum of squares of y = acc + bv
+// over the group's points < N, to stats[m * P + gi] (rows m = mg + ... < M).
+template <int SI, int NA>
+__device__ __forceinline__ void group_stats(const f32x16 (&acc)[SI][NA], int i,
+                                            const float (&bv)[16], int g0, int N, int mg, int M,
+                                            int r, int h, float2* __restrict__ stats, int P,
+                                            int gi) {
+  const int nv = min(32 * NA, N - g0);
+  float v[32], sr = 0.0f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const float v0 = acc[i][0][e] + bv[e];
+    const float s0 = __builtin_bit_cast(
+        float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v0), 0));
+    const float s1 = __builtin_bit_cast(
+        float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v0), 32));
+    const float sh = h ? s1 : s0;  // row (e, h)'s value at point g0
+    sr = r == e ? sh : sr;
+    const float d0 = g0 + r < N ? v0 - sh : 0.0f;
+    float s = d0, q = d0 * d0;  // (no zero start value: -0.0f + 0.0f is +0.0f)
+#pragma unroll
+    for (int j = 1; j < NA; ++j) {
+      const float dj = g0 + 32 * j + r < N ? acc[i][j][e] + bv[e] - sh : 0.0f;
+      s = s + dj;
+      q = __builtin_fmaf(dj, dj, q);
+    }
+    v[e] = s;
+    v[16 + e] = q;
+  }
+  xpose_reduce_stage<32, 16>(v, r & 16);
+  xpose_reduce_stage<16, 8>(v, r & 8);
+  xpose_reduce_stage<8, 4>(v, r & 4);
+  xpose_reduce_stage<4, 2>(v, r & 2);
+  xpose_reduce_stage<2, 1>(v, r & 1);
+  // lane r: v[0] = sum of value r (r < 16: shifted sum of row e = r; else its squares)
+  const float q = swz_xor<16>(v[0]);
+  const int m = mg + acc_row(r & 15, h);
+  if (r < 16 && m < M) {
+    const float a = v[0], mu_s = a / (float)nv;
+    stats[(size_t)m * P + gi] = make_float2(sr + mu_s, fmaxf(__builtin_fmaf(-a, mu_s, q), 0.0f));
+  }
+}
+
 // Epilogue of a 256 (m) x 128 (point) tile held as 8 waves of 64 x 64
 // (pw_gemm256_kernel): y = acc + bias, streamed stores, and with stats the
 // per-(channel, 64-point group) BatchNorm statistics (see pw_gemm256_kernel).
@@ -220,51 +255,19 @@ __device__ __forceinline__ void pw256_epilogue(const f32x16 (&acc)[2][2], const 
     const int mg = m0 + wr * 64 + i * 32;
     float* __restrict__ yr = y.row(b, min(mg, M - 1), N);
     float bv[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) bv[e] = sbias[mg - m0 + (e & 3) + 8 * (e >> 2) + 4 * h];
+    lds_bias16(sbias, mg - m0, h, bv);
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int dm = (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int dm = acc_row(e, h);
         const int m = mg + dm;
         const int p = pw0 + j * 32 + r;
-#ifdef PCFM_EXP_PW_NOSTORE
-        if (acc[i][j][e] == 1.2345f)
-#endif
         if (m < M && p < N) out_store(yr + (size_t)dm * N + p, acc[i][j][e] + bv[e]);
       }
     if (stats != nullptr && pw0 < N) {
-      const int nv = min(64, N - pw0);
-      const int ngroups = (N + 63) / 64, P = nb * ngroups;
-      const bool ok0 = pw0 + r < N, ok1 = pw0 + 32 + r < N;
-      float v[32], sr = 0.0f;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float v0 = acc[i][0][e] + bv[e], v1 = acc[i][1][e] + bv[e];
-        const float s0 = __builtin_bit_cast(
-            float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v0), 0));
-        const float s1 = __builtin_bit_cast(
-            float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v0), 32));
-        const float sh = h ? s1 : s0;  // row (e, h)'s value at point pw0
-        sr = r == e ? sh : sr;
-        const float d0 = ok0 ? v0 - sh : 0.0f, d1 = ok1 ? v1 - sh : 0.0f;
-        v[e] = d0 + d1;
-        v[16 + e] = __builtin_fmaf(d1, d1, d0 * d0);
-      }
-      xpose_reduce_stage<32, 16>(v, r & 16);
-      xpose_reduce_stage<16, 8>(v, r & 8);
-      xpose_reduce_stage<8, 4>(v, r & 4);
-      xpose_reduce_stage<4, 2>(v, r & 2);
-      xpose_reduce_stage<2, 1>(v, r & 1);
-      // lane r: v[0] = sum of value r (r < 16: shifted sum of row e = r; else its squares)
-      const float q = swz_xor<16>(v[0]);
-      const int m = mg + (r & 3) + 8 * ((r >> 2) & 3) + 4 * h;
-      if (r < 16 && m < M) {
-        const float a = v[0], mu_s = a / (float)nv;
-        stats[(size_t)m * P + b * ngroups + pw0 / 64] =
-            make_float2(sr + mu_s, fmaxf(__builtin_fmaf(-a, mu_s, q), 0.0f));
-      }
+      const int ngroups = (N + 63) / 64;
+      group_stats(acc, i, bv, pw0, N, mg, M, r, h, stats, nb * ngroups, b * ngroups + pw0 / 64);
     }
   }
 }
@@ -305,9 +308,6 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
       const_cast<uint16_t*>(wl), (short)0, 0x7FFFFFF0, 0x00020000);
   const int aoff = ((m0 + arow) * Kpad + ahalf) * 2;
   auto load_a = [&](int s) {
-#ifdef PCFM_EXP_PW_NOW
-    if (s > 0) return;
-#endif
     const int so = s * kKT * 2;
     ra0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rwh, aoff, so, 0));
     ra1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rwh, aoff, so + 16, 0));
@@ -327,13 +327,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
 #pragma unroll
     for (int q = 0; q < CPT; ++q) {
       const int c = c0 + ch + q;
-#ifdef PCFM_EXP_PW_NOX
-      v[q] = (float)(c + voff);
-      (void)rs;
-#else
       v[q] = __builtin_bit_cast(
           float, __builtin_amdgcn_raw_buffer_load_b32(rs, voff, (c < K ? c - cb : 0) * N * 4, 0));
-#endif
     }
   };
   // the padding (points >= N, channels >= K) is zeroed at the store
@@ -351,42 +346,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
   };
 
   f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
-
-  auto frag = [&](int o) {
-    return __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(lds + o));
-  };
-  auto mfma_step = [&]() {
-#pragma unroll
-    for (int kk = 0; kk < kKT / 16; ++kk) {
-      bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int o = (wr * 64 + i * 32 + r) * kLDR + kk * 16 + 8 * h;
-        ah[i] = frag(o);
-        al[i] = frag(A_ELEMS + o);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int o = 2 * A_ELEMS + (wc * 64 + j * 32 + r) * kLDR + kk * 16 + 8 * h;
-        bh[j] = frag(o);
-        bl[j] = frag(B_ELEMS + o);
-      }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-        }
-    }
-  };
+  zero_acc(acc);
 
   load_a(0);
   load_b(0, rb);
@@ -400,11 +360,8 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
     // keep the loads in front of the MFMA work (left to itself the scheduler
     // sinks the weight loads to the end of the step)
     __builtin_amdgcn_sched_barrier(0);
-#ifndef PCFM_EXP_PW_NOMFMA
-    mfma_step();
-#else
-    acc[0][0][0] += (float)lds[t];
-#endif
+    lds_mfma_x3(lds, lds + A_ELEMS, wr * 64 + r, lds + 2 * A_ELEMS, lds + 2 * A_ELEMS + B_ELEMS,
+                wc * 64 + r, kLDR, h, acc);
     __syncthreads();
     if (s + 1 < nsteps) store(s + 1, rb);
     __syncthreads();
@@ -426,19 +383,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))
 // chunk's 24 MFMAs run.  LDS rows of Kpad + 8 bf16 keep the ds_read_b128
 // fragment reads conflict-free.  grid = min(tiles / 8, CUs x blocks per CU),
 // 512 threads.
+// (Removed: an opt-in form that held B-operand chunks two ahead in registers,
+// twice the bytes in flight; it never became the default and had neither the
+// statistics epilogue nor the LDS bias.)
 constexpr int kSW = 8;  // waves per streaming block
-#ifndef PCFM_PW_STREAM_PF
-#define PCFM_PW_STREAM_PF 1  // B-operand chunks prefetched (1 or 2)
-#endif
-__device__ __forceinline__ bf16x8 split8(const float (&v)[8], bf16x8& lo) {
-  bf16x8 hi;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    hi[j] = (__bf16)v[j];
-    lo[j] = (__bf16)(v[j] - (float)hi[j]);
-  }
-  return hi;
-}
 
 __device__ __forceinline__ const float* uniform_ptr(const float* p) {
   const unsigned long long u = (unsigned long long)p;
@@ -480,19 +428,16 @@ __global__ void __launch_bounds__(kSW * 64)
   constexpr int Kpad = 32 * NCH, ldr = Kpad + 8, cpr = Kpad / 8;
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
-  // blockIdx.y: the block's 128-row slice of the output channels (M > 128:
-  // every slice streams all point tiles; slices of a tile share its x reads
-  // in L2 -- blocks (x, y) and (x, y') sit on one XCD when gridDim.x % 8 == 0)
-  const int m0 = (int)blockIdx.y * 128;
-  // one bias shared by the batch: the slice's 128 rows staged in LDS with the
+  // (The M > 128 form in 128-row slices along blockIdx.y was removed: see pw_plan.)
+  // one bias shared by the batch: the 128 rows staged in LDS with the
   // weights, so a tile's epilogue does not wait on global loads
   __shared__ float sbias[128];
   const bool lbias = bias != nullptr && bias_bstride == 0;
-  if (lbias && t < 128) sbias[t] = bias[min(m0 + t, M - 1)];
+  if (lbias && t < 128) sbias[t] = bias[min(t, M - 1)];
   for (int e = t; e < 2 * 128 * cpr; e += kSW * 64) {  // weight image -> LDS, 16-B pieces
     const int img = e / (128 * cpr), rem = e - img * 128 * cpr;
     const int row = rem / cpr, pc = rem - row * cpr;
-    const uint16_t* src = (img ? wl : wh) + (size_t)(m0 + row) * Kpad + pc * 8;
+    const uint16_t* src = (img ? wl : wh) + (size_t)row * Kpad + pc * 8;
     *reinterpret_cast<uint4*>(sa + img * 128 * ldr + row * ldr + pc * 8) =
         *reinterpret_cast<const uint4*>(src);
   }
@@ -505,91 +450,6 @@ __global__ void __launch_bounds__(kSW * 64)
   if (tl >= tiles) return;  // wave-uniform; no barrier below
   const uint16_t* sah = sa;
   const uint16_t* sal = sa + 128 * ldr;
-#if PCFM_PW_STREAM_PF >= 2
-  // B-operand chunks two ahead in registers: (tile, chunk) positions walk the
-  // wave's tiles chunk by chunk; while chunk s computes, s+1 and s+2 are in
-  // flight (twice the bytes in flight of the one-ahead form)
-  auto adv = [&](int& t, int& c) {
-    if (++c == NCH) {
-      c = 0;
-      t += wstride;
-    }
-  };
-  auto load_at = [&](int t, int c, float (&v)[16]) {
-    const int bb = __builtin_amdgcn_readfirstlane(t / ntn);
-    pw_stream_load(x, bb, 32 * c, N, (t - bb * ntn) * 32 + n, h, v);
-  };
-  int t1 = tl, c1 = 0;
-  adv(t1, c1);
-  int t2 = t1, c2 = c1;
-  adv(t2, c2);
-  float nx[16], nx1[16];
-  load_at(tl, 0, nx);
-  if (t1 < tiles) load_at(t1, c1, nx1);
-  int ck = 0;
-  f32x16 acc[4];
-  while (true) {
-    const int b = __builtin_amdgcn_readfirstlane(tl / ntn);
-    const int p = (tl - b * ntn) * 32 + n;
-    float cur[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      cur[q] = nx[q];
-      nx[q] = nx1[q];
-    }
-    if (t2 < tiles) load_at(t2, c2, nx1);
-    if (ck == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][e] = 0.0f;
-    }
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      bf16x8 bh, bl;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        bh[j] = (__bf16)cur[8 * kk + j];
-        bl[j] = (__bf16)(cur[8 * kk + j] - (float)bh[j]);
-      }
-      const int ko = ck * 32 + kk * 16 + 8 * h;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int o = (32 * i + n) * ldr + ko;
-        const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sah + o));
-        const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sal + o));
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i], 0, 0, 0);
-        acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i], 0, 0, 0);
-      }
-    }
-    if (ck == NCH - 1) {
-      const int bo = b * bias_bstride;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int mg = m0 + 32 * i;
-        if (mg < M) {
-          float* __restrict__ yr = const_cast<float*>(uniform_ptr(y.row(b, mg, N)));
-          float* __restrict__ yl = yr + 4 * h * N + p;
-          float bv[16];
-          const float* bl = bias != nullptr ? uniform_ptr(bias + bo + mg) + 4 * h : nullptr;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) bv[e] = bl != nullptr ? bl[(e & 3) + 8 * (e >> 2)] : 0.0f;
-          if (p < N) {
-#pragma unroll
-            for (int e = 0; e < 16; ++e)
-              out_store(yl + ((e & 3) + 8 * (e >> 2)) * N, acc[i][e] + bv[e]);
-          }
-        }
-      }
-    }
-    adv(tl, ck);
-    adv(t1, c1);
-    adv(t2, c2);
-    if (tl >= tiles) break;
-  }
-}
-#else
   float nx[16];
   {
     const int b = tl / ntn;
@@ -601,11 +461,8 @@ __global__ void __launch_bounds__(kSW * 64)
     const int ntl = tl + wstride;  // the next tile's chunk 0 is issued during chunk NCH-1
     const int nb = __builtin_amdgcn_readfirstlane(ntl / ntn);
     const int np = (ntl - nb * ntn) * 32 + n;
-    f32x16 acc[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][e] = 0.0f;
+    f32x16 acc[4][1];  // 128 rows x this wave's 32 points
+    zero_acc(acc);
 #pragma unroll 1
     for (int ck = 0; ck < NCH; ++ck) {
       float cur[16];
@@ -618,29 +475,23 @@ __global__ void __launch_bounds__(kSW * 64)
       }
 #pragma unroll
       for (int kk = 0; kk < 2; ++kk) {
-        bf16x8 bh, bl;
+        bf16x8 ah[4], al[4], bh[1], bl[1];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          bh[j] = (__bf16)cur[8 * kk + j];
-          bl[j] = (__bf16)(cur[8 * kk + j] - (float)bh[j]);
+          bh[0][j] = (__bf16)cur[8 * kk + j];
+          bl[0][j] = (__bf16)(cur[8 * kk + j] - (float)bh[0][j]);
         }
         const int ko = ck * 32 + kk * 16 + 8 * h;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int o = (32 * i + n) * ldr + ko;
-          const bf16x8 ah = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sah + o));
-          const bf16x8 al = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(sal + o));
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc[i], 0, 0, 0);
-          acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc[i], 0, 0, 0);
-        }
+        for (int i = 0; i < 4; ++i) lds_frag(sah, sal, (32 * i + n) * ldr + ko, ah[i], al[i]);
+        mfma_x3_interleaved(ah, al, bh, bl, acc);
       }
     }
-    // epilogue: rows 32 i + (e & 3) + 8 (e >> 2) + 4 h, point p
+    // epilogue: rows 32 i + acc_row(e, h), point p
     const int bo = b * bias_bstride;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int mg = m0 + 32 * i;
+      const int mg = 32 * i;
       if (mg < M) {
         // a 32-row group lies in one output part
         float* __restrict__ yr = const_cast<float*>(uniform_ptr(y.row(b, mg, N)));
@@ -651,46 +502,18 @@ __global__ void __launch_bounds__(kSW * 64)
         float bv[16];
         const float* bl = bias != nullptr ? uniform_ptr(bias + bo + mg) + 4 * h : nullptr;
         if (lbias) {  // block-uniform
-#pragma unroll
-          for (int e = 0; e < 16; ++e) bv[e] = sbias[32 * i + (e & 3) + 8 * (e >> 2) + 4 * h];
+          lds_bias16(sbias, mg, h, bv);
         } else {
 #pragma unroll
-          for (int e = 0; e < 16; ++e) bv[e] = bl != nullptr ? bl[(e & 3) + 8 * (e >> 2)] : 0.0f;
+          for (int e = 0; e < 16; ++e) bv[e] = bl != nullptr ? bl[acc_row(e, 0)] : 0.0f;
         }
         if (p < N) {
 #pragma unroll
-          for (int e = 0; e < 16; ++e) out_store(yl + ((e & 3) + 8 * (e >> 2)) * N, acc[i][e] + bv[e]);
+          for (int e = 0; e < 16; ++e) out_store(yl + acc_row(e, 0) * N, acc[i][0][e] + bv[e]);
         }
         if (ST) {
-          const int p0 = p - n, nv = min(32, N - p0);
-          const int ngroups = (N + 31) / 32, P = B * ngroups;
-          const bool ok = p < N;
-          float v[32], sr = 0.0f;
-#pragma unroll
-          for (int e = 0; e < 16; ++e) {
-            const float v0 = acc[i][e] + bv[e];
-            const float s0 = __builtin_bit_cast(
-                float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v0), 0));
-            const float s1 = __builtin_bit_cast(
-                float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v0), 32));
-            const float sh = h ? s1 : s0;  // row (e, h)'s value at point p0
-            sr = n == e ? sh : sr;
-            const float d0 = ok ? v0 - sh : 0.0f;
-            v[e] = d0;
-            v[16 + e] = d0 * d0;
-          }
-          xpose_reduce_stage<32, 16>(v, n & 16);
-          xpose_reduce_stage<16, 8>(v, n & 8);
-          xpose_reduce_stage<8, 4>(v, n & 4);
-          xpose_reduce_stage<4, 2>(v, n & 2);
-          xpose_reduce_stage<2, 1>(v, n & 1);
-          const float q = swz_xor<16>(v[0]);
-          const int m = mg + (n & 3) + 8 * ((n >> 2) & 3) + 4 * h;
-          if (n < 16 && m < M) {
-            const float a = v[0], mu_s = a / (float)nv;
-            stats[(size_t)m * P + b * ngroups + p0 / 32] =
-                make_float2(sr + mu_s, fmaxf(__builtin_fmaf(-a, mu_s, q), 0.0f));
-          }
+          const int p0 = p - n, ngroups = (N + 31) / 32;
+          group_stats(acc, i, bv, p0, N, mg, M, n, h, stats, B * ngroups, b * ngroups + p0 / 32);
         }
       }
     }
@@ -698,16 +521,10 @@ __global__ void __launch_bounds__(kSW * 64)
     if (tl >= tiles) break;
   }
 }
-#endif
 
 // dW partials: grid = (ceil(Cout/128) * ceil(Cin/128), S); K-steps of 32
 // points (a step never crosses a batch element).  part [S][Cout][Cin].
-#ifdef PCFM_PW_WG_WAVES
-#define PW_WG_WAVES __attribute__((amdgpu_waves_per_eu(PCFM_PW_WG_WAVES, PCFM_PW_WG_WAVES)))
-#else
-#define PW_WG_WAVES
-#endif
-__global__ void __launch_bounds__(256) PW_WG_WAVES
+__global__ void __launch_bounds__(256)
     pw_wgrad_kernel(const Parts x, const float* __restrict__ dy, int B, int cin,
                     int cout, int N, int S, float* __restrict__ part) {
   using T = Tile<128, 128>;
@@ -766,19 +583,19 @@ __global__ void __launch_bounds__(256) PW_WG_WAVES
       }
     }
   };
-  auto store = [&](uint16_t* buf) {
+  auto store = [&]() {
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       ra[q] = (amask >> q) & 1u ? 0.0f : ra[q];
       rb[q] = (bmask >> q) & 1u ? 0.0f : rb[q];
     }
-    uint16_t* ah = buf + srow * kLDR + shalf;
+    uint16_t* ah = lds + srow * kLDR + shalf;
     store_split<16>(ra, ah, ah + T::A_ELEMS);
-    uint16_t* bh = buf + 2 * T::A_ELEMS + srow * kLDR + shalf;
+    uint16_t* bh = lds + 2 * T::A_ELEMS + srow * kLDR + shalf;
     store_split<16>(rb, bh, bh + T::B_ELEMS);
   };
 
-  f32x16 acc[2][2];
+  f32x16 acc[2][2];  // (zeroed in place: zero_acc costs this kernel 4 VGPRs)
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -788,14 +605,14 @@ __global__ void __launch_bounds__(256) PW_WG_WAVES
 
   if (k0 < k1) {
     load(k0);
-    store(lds);
+    store();
   }
   __syncthreads();
   for (long long ks = k0; ks < k1; ++ks) {
     if (ks + 1 < k1) load(ks + 1);
     tile_mfma<128, 128>(lds, wr, wc, r, h, acc);
     __syncthreads();
-    if (ks + 1 < k1) store(lds);
+    if (ks + 1 < k1) store();
     __syncthreads();
   }
   float* pb = part + (size_t)sp * cout * cin;
@@ -805,7 +622,7 @@ __global__ void __launch_bounds__(256) PW_WG_WAVES
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int o = co0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int o = co0 + wr * 64 + i * 32 + acc_row(e, h);
         const int c = ci0 + wc * 64 + j * 32 + r;
         if (o < cout && c < cin) pb[(size_t)o * cin + c] = acc[i][j][e];
       }
@@ -814,6 +631,9 @@ __global__ void __launch_bounds__(256) PW_WG_WAVES
 // Wide form for cout, cin multiples of 256 (one 256 x 256 tile): 512 threads,
 // 8 waves of 64 (co) x 128 (ci), so dY and x rows are each read once per
 // K-range instead of cin/128 resp. cout/128 times; 80 KiB LDS, one block per CU.
+// (A ragged last input-channel tile, cin % 256 != 0, was supported and masked
+// here; it measured slower than the 128 x 128 tiles -- see pw_wgrad_plan -- and
+// no shape reached it, so the kernel takes whole tiles only.)
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
     pw_wgrad256_kernel(const Parts x, const float* __restrict__ dy, int B, int cin, int cout,
                        int N, int S, float* __restrict__ part) {
@@ -831,13 +651,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   const int wr = w >> 1, wc = w & 1, r = lane & 31, h = lane >> 5;  // wr 0..3 (co), wc 0..1 (ci)
   const int srow = t >> 1, shalf = (t & 1) * 16;                     // row 0..255, 16-point half
   const int co = co0 + srow, ci = ci0 + srow;
-  // a ragged last input-channel tile (cin % 256 != 0): rows past cin read the
-  // last row and are zeroed
-  const bool ciok = ci < cin;
-  const int cic = ciok ? ci : cin - 1;
   const bool vec = (N & 3) == 0;
-  const float* __restrict__ xrow = x.row(0, cic, N);
-  const size_t xbstride = (size_t)(x.row(1, cic, N) - xrow);
+  const float* __restrict__ xrow = x.row(0, ci, N);
+  const size_t xbstride = (size_t)(x.row(1, ci, N) - xrow);
 
   float ra[16], rb[16];
   uint32_t pmask = 0u;
@@ -876,7 +692,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
       ra[q] = (pmask >> q) & 1u ? 0.0f : ra[q];
-      rb[q] = ((pmask >> q) & 1u) || !ciok ? 0.0f : rb[q];
+      rb[q] = (pmask >> q) & 1u ? 0.0f : rb[q];
     }
     uint16_t* ah = lds + srow * kLDR + shalf;
     store_split<16>(ra, ah, ah + A_ELEMS);
@@ -885,12 +701,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   };
 
   f32x16 acc[2][4];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+  zero_acc(acc);
 
   if (k0 < k1) {
     load(k0);
@@ -899,6 +710,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
   __syncthreads();
   for (long long ks = k0; ks < k1; ++ks) {
     if (ks + 1 < k1) load(ks + 1);
+    // (written out: through lds_mfma_x3<2, 4> the kernel takes 248 VGPRs instead of 230)
 #pragma unroll
     for (int kk = 0; kk < kKT / 16; ++kk) {
       bf16x8 ah[2], al[2], bh[4], bl[4];
@@ -914,14 +726,7 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
         bh[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(lds + o));
         bl[j] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(lds + B_ELEMS + o));
       }
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], acc[i][j], 0, 0, 0);
-        }
+      mfma_x3_interleaved(ah, al, bh, bl, acc);
     }
     __syncthreads();
     if (ks + 1 < k1) store();
@@ -934,9 +739,9 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int o = co0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int o = co0 + wr * 64 + i * 32 + acc_row(e, h);
         const int c = ci0 + wc * 128 + j * 32 + r;
-        if (c < cin) pb[(size_t)o * cin + c] = acc[i][j][e];
+        pb[(size_t)o * cin + c] = acc[i][j][e];
       }
 }
 
@@ -966,39 +771,32 @@ __global__ void __launch_bounds__(256)
   if (grp == 0 && i < total) dw[i] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
 }
 
-bool pw_wgrad_wide(int cin, int cout) {
-#ifdef PCFM_PW_NO256
-  return false;
-#else
-  // (a ragged last input-channel tile is supported and masked, but measured
-  // slower than the 128 x 128 tiles for ContextNet head_pre, cin = 640: 378 vs
-  // 290 us -- one block per CU over a half-empty third tile)
-  return cin % 256 == 0 && cout % 256 == 0;
-#endif
-}
-
-int pw_wgrad_splits(int B, int cin, int cout, int N) {
-  if (pw_wgrad_wide(cin, cout)) {  // one 512-thread block per CU
-    const long long tiles = (long long)(cout / 256) * ((cin + 255) / 256);
-    const long long steps = (long long)B * ((N + kKT - 1) / kKT);
-    long long s = std::max(1LL, ((long long)kCUs + tiles - 1) / tiles);
-    s = std::min(s, std::max(1LL, steps / 16));
-    return (int)std::min(s, 256LL);
-  }
-#ifndef PCFM_PW_WG_BPC
-#define PCFM_PW_WG_BPC 2  // target blocks per CU
-#endif
-#ifndef PCFM_PW_WG_MINSTEPS
-#define PCFM_PW_WG_MINSTEPS 8  // K-steps per split at least
-#endif
-#ifndef PCFM_PW_WG_CAP
-#define PCFM_PW_WG_CAP 512  // splits at most (128: 72 -> 49 us at C128, tools/pw_ab.py)
-#endif
-  const long long tiles = (long long)((cout + 127) / 128) * ((cin + 127) / 128);
+// The weight gradient's kernel, grid and workspace for a shape: ONE decision,
+// used by the workspace query and the launcher.
+constexpr int kWgBpc = 2;       // 128 x 128 tiles: target blocks per CU
+constexpr int kWgMinSteps = 8;  // K-steps per split at least
+constexpr int kWgCap = 512;     // splits at most (128: 72 -> 49 us at C128, tools/pw_ab.py)
+struct PwWgradPlan {
+  bool wide;          // pw_wgrad256_kernel (256 x 256 tiles), else pw_wgrad_kernel (128 x 128)
+  int tiles, splits;  // the grid: (tiles, splits)
+  size_t part_bytes;  // the partials [splits][cout][cin]
+};
+PwWgradPlan pw_wgrad_plan(int B, int cin, int cout, int N) {
+  PwWgradPlan p;
+  // (a ragged last input-channel tile of the wide form measured slower than the
+  // 128 x 128 tiles for ContextNet head_pre, cin = 640: 378 vs 290 us -- one
+  // block per CU over a half-empty third tile)
+  p.wide = cin % 256 == 0 && cout % 256 == 0;
+  const int T = p.wide ? 256 : 128;
+  p.tiles = ((cout + T - 1) / T) * ((cin + T - 1) / T);
+  // wide: one 512-thread block per CU, 16 K-steps per split at least, 256 splits at most
+  const long long bpc = p.wide ? 1 : kWgBpc, minsteps = p.wide ? 16 : kWgMinSteps;
   const long long steps = (long long)B * ((N + kKT - 1) / kKT);
-  long long s = std::max(1LL, ((long long)PCFM_PW_WG_BPC * kCUs + tiles - 1) / tiles);
-  s = std::min(s, std::max(1LL, steps / PCFM_PW_WG_MINSTEPS));
-  return (int)std::min(s, (long long)PCFM_PW_WG_CAP);
+  long long s = std::max(1LL, (bpc * kCUs + p.tiles - 1) / p.tiles);
+  s = std::min(s, std::max(1LL, steps / minsteps));
+  p.splits = (int)std::min(s, p.wide ? 256LL : (long long)kWgCap);
+  p.part_bytes = (size_t)p.splits * cout * cin * sizeof(float);
+  return p;
 }
 
 bool pw_ok(int b, int cin, int cout, int n) {
@@ -1031,61 +829,63 @@ extern "C" int pcfm_pointwise_prep_weight(const float* w, int cout, int cin, int
   return check_launch("pointwise_prep_weight");
 }
 
-// The forward GEMM's kernel for a shape: ONE decision, used by the launcher
-// and by pcfm_pointwise_bnstats_groups(), so a caller is never told that a
-// shape writes BatchNorm statistics when the kernel that runs does not.
+// The forward GEMM's kernel and launch geometry for a shape: ONE decision, used
+// by the launcher and by pcfm_pointwise_bnstats_groups(), so a caller is never
+// told that a shape writes BatchNorm statistics when the kernel that runs does not.
 // (Measured and removed in round 6, with their A/B final: the 128-row streaming
 // kernel in 128-row slices for M > 128 -- correct, slower: 256->256 forward 98.9
 // vs 88.9 us, profiles/r05_ab_pw_stream_m.jsonl -- and the persistent LDS-DMA
 // 256-row form -- bit-identical, 106.6 vs 94.0 us, profiles/r05_ab_pw_glds256.jsonl.)
 enum class PwPath { Stream128, Tile256, Tile128, Tile64 };
+struct PwPlan {
+  PwPath path;
+  int Mpad, Kpad;  // the weight image [Mpad][Kpad], hi then lo
+  dim3 grid, block;
+  size_t lds;       // dynamic LDS bytes
+  int stats_group;  // points per BatchNorm statistics group; 0: no statistics epilogue
+};
 
-static PwPath pw_path(int b, int cin, int cout, int n) {
-  const int Mpad = pw_mpad(cout), Kpad = pad_to(cin, kKT);
-  const long long big = (long long)ceil_div(n, 128) * (Mpad / 128) * b;
-#ifndef PCFM_PW_NOSTREAM
-  if (Mpad == 128 && Kpad <= 256 && cin % 32 == 0 && cout % 32 == 0) return PwPath::Stream128;
-#endif
-#ifndef PCFM_PW_NO256
-  if (Mpad % 256 == 0 && big / 2 >= 2 * kCUs) return PwPath::Tile256;
-#endif
-  return big >= 2 * kCUs ? PwPath::Tile128 : PwPath::Tile64;
-}
-
-// The 256-row tiles (64-point groups) and the 128-row streaming form (32-point
-// groups) have the statistics epilogue.
-static bool pw_path_has_stats(PwPath p) {
-  if (p == PwPath::Stream128) {  // PCFM_PW_STREAM_STATS=0: measurement switch
+static PwPlan pw_plan(int b, int cin, int cout, int n) {
+  PwPlan p{};
+  p.Mpad = pw_mpad(cout);
+  p.Kpad = pad_to(cin, kKT);
+  const long long big = (long long)ceil_div(n, 128) * (p.Mpad / 128) * b;
+  if (p.Mpad == 128 && p.Kpad <= 256 && cin % 32 == 0 && cout % 32 == 0) {
+    p.path = PwPath::Stream128;
+    p.lds = (size_t)2 * 128 * (p.Kpad + 8) * sizeof(uint16_t);
+    const long long tiles = (long long)b * ceil_div(n, 32);
+    const long long cap = (long long)kCUs * (p.lds <= 80 * 1024 ? 2 : 1);  // blocks per CU
+    p.grid = dim3((int)std::max(1LL, std::min((tiles + kSW - 1) / kSW, cap)));
+    p.block = dim3(kSW * 64);
+    // PCFM_PW_STREAM_STATS=0: measurement switch
     const char* e = std::getenv("PCFM_PW_STREAM_STATS");
-    return PCFM_PW_STREAM_PF < 2 && (e == nullptr || e[0] != '0');
+    p.stats_group = e == nullptr || e[0] != '0' ? 32 : 0;
+    return p;
   }
-  return p == PwPath::Tile256;
+  // the 256-row tile where it fills the chip twice, else 128-row or 64-row tiles
+  const bool t256 = p.Mpad % 256 == 0 && big / 2 >= 2 * kCUs;
+  p.path = t256 ? PwPath::Tile256 : big >= 2 * kCUs ? PwPath::Tile128 : PwPath::Tile64;
+  const int TM = t256 ? 256 : p.path == PwPath::Tile128 ? 128 : 64, TN = std::min(TM, 128);
+  p.grid = dim3(ceil_div(n, TN), p.Mpad / TM, b);
+  p.block = dim3(t256 ? 512 : 256);
+  p.stats_group = t256 ? 64 : 0;
+  return p;
 }
-static int pw_stats_group(PwPath p) { return p == PwPath::Stream128 ? 32 : 64; }
 
 static int pw_gemm_launch(const Parts& x, const void* wsplit, const float* bias, int bias_bstride,
                           int b, int cin, int cout, int n, const Parts& y, hipStream_t st,
                           float2* stats = nullptr) {
-  const int Mpad = pw_mpad(cout), Kpad = pad_to(cin, kKT);
-  const size_t total = (size_t)Mpad * Kpad;
+  const PwPlan p = pw_plan(b, cin, cout, n);
   const uint16_t* wh = (const uint16_t*)wsplit;
-  const PwPath path = pw_path(b, cin, cout, n);
+  const uint16_t* wl = wh + (size_t)p.Mpad * p.Kpad;
   // a statistics request the chosen kernel cannot serve fails loudly (it used
   // to be dropped, leaving the caller's stats buffer unwritten)
-  PCFM_CHECK_ARG(stats == nullptr || pw_path_has_stats(path),
+  PCFM_CHECK_ARG(stats == nullptr || p.stats_group > 0,
                  "pointwise_gemm: BatchNorm statistics requested for a shape whose kernel has "
                  "no statistics epilogue (b=%d cin=%d cout=%d n=%d)", b, cin, cout, n);
-  if (path == PwPath::Stream128) {
-    const uint16_t* wl_img = wh + total;
-    const long long tiles = (long long)b * ceil_div(n, 32);
-    const size_t lds = (size_t)2 * 128 * (Kpad + 8) * sizeof(uint16_t);
-    const int per_cu = lds <= 80 * 1024 ? 2 : 1;
-    const int slices = Mpad / 128;
-    // the slices share the chip: grid.x a multiple of 8 (XCD pairing, see the kernel)
-    const long long cap = std::max(8LL, ((long long)kCUs * per_cu / slices) & ~7LL);
-    const int grid = (int)std::max(1LL, std::min((tiles + kSW - 1) / kSW, cap));
+  if (p.path == PwPath::Stream128) {
     const void* kfn = nullptr;
-    switch (Kpad / 32) {
+    switch (p.Kpad / 32) {
 #define PW_STREAM_CASE(NC)                                                                 \
   case NC:                                                                                 \
     kfn = stats != nullptr ? (const void*)pw_stream128_kernel<NC, true>                    \
@@ -1097,32 +897,27 @@ static int pw_gemm_launch(const Parts& x, const void* wsplit, const float* bias,
     }
     const int e = allow_big_lds(kfn);
     if (e) return e;
-    void* args[] = {(void*)&x,    (void*)&wh,  (void*)&wl_img, (void*)&bias,
+    void* args[] = {(void*)&x,    (void*)&wh,  (void*)&wl, (void*)&bias,
                     (void*)&bias_bstride, (void*)&y, (void*)&cin, (void*)&cout,
                     (void*)&n,    (void*)&b,   (void*)&stats};
-    const hipError_t le = hipLaunchKernel(kfn, dim3(grid, slices), dim3(kSW * 64), args, lds, st);
+    const hipError_t le = hipLaunchKernel(kfn, p.grid, p.block, args, p.lds, st);
     if (le != hipSuccess) {
       set_error("pointwise_gemm: launch failed");
       return (int)le;
     }
-    return check_launch("pointwise_gemm");
-  }
-  if (path == PwPath::Tile256) {
-    const dim3 g256(ceil_div(n, 128), Mpad / 256, b);
-    hipLaunchKernelGGL(pw_gemm256_kernel, g256, dim3(512), 0, st, x, wh, wh + total, bias,
-                       bias_bstride, y, cin, cout, n, Kpad, stats);
-    return check_launch("pointwise_gemm");
-  }
-  if (path == PwPath::Tile128) {
-    hipLaunchKernelGGL((pw_gemm_kernel<128, 128>), dim3(ceil_div(n, 128), Mpad / 128, b),
-                       dim3(256), 0, st, x, wh, wh + total, bias, bias_bstride, y, cin, cout, n,
-                       Kpad);
+  } else if (p.path == PwPath::Tile256) {
+    hipLaunchKernelGGL(pw_gemm256_kernel, p.grid, p.block, 0, st, x, wh, wl, bias, bias_bstride, y,
+                       cin, cout, n, p.Kpad, stats);
+  } else if (p.path == PwPath::Tile128) {
+    hipLaunchKernelGGL((pw_gemm_kernel<128, 128>), p.grid, p.block, 0, st, x, wh, wl, bias,
+                       bias_bstride, y, cin, cout, n, p.Kpad);
   } else {
-    hipLaunchKernelGGL((pw_gemm_kernel<64, 64>), dim3(ceil_div(n, 64), Mpad / 64, b), dim3(256),
-                       0, st, x, wh, wh + total, bias, bias_bstride, y, cin, cout, n, Kpad);
+    hipLaunchKernelGGL((pw_gemm_kernel<64, 64>), p.grid, p.block, 0, st, x, wh, wl, bias,
+                       bias_bstride, y, cin, cout, n, p.Kpad);
   }
   return check_launch("pointwise_gemm");
 }
+
 
 // host arrays -> Parts; every width a multiple of `align` (the last may be ragged)
 static bool make_parts(int np, float* const* ptr, const int* width, int align, Parts& q,
@@ -1157,9 +952,8 @@ extern "C" int pcfm_pointwise_gemm(const float* x, const void* wsplit, const flo
 // pcfm_pointwise_bnstats_groups() > 0 for the shapes that take this path.
 extern "C" int pcfm_pointwise_bnstats_groups(int b, int cin, int cout, int n) {
   if (!pw_ok(b, cin, cout, n) || b <= 0 || n <= 0) return 0;
-  const PwPath p = pw_path(b, cin, cout, n);
-  if (!pw_path_has_stats(p)) return 0;
-  return b * ceil_div(n, pw_stats_group(p));
+  const int group = pw_plan(b, cin, cout, n).stats_group;
+  return group > 0 ? b * ceil_div(n, group) : 0;
 }
 
 extern "C" int pcfm_pointwise_gemm_bnstats(const float* x, const void* wsplit, const float* bias,
@@ -1190,25 +984,26 @@ extern "C" int pcfm_pointwise_gemm_parts(int nx, const float* const* x, const in
 }
 
 static int pw_wgrad_launch(const Parts& x, const float* grad_y, int b, int cin, int cout, int n,
-                           float* grad_w, void* ws, hipStream_t st) {
+                           float* grad_w, void* ws, size_t ws_bytes, hipStream_t st) {
   const size_t total = (size_t)cout * cin;
-  const int S = pw_wgrad_splits(b, cin, cout, n);
-  if (pw_wgrad_wide(cin, cout)) {
-    hipLaunchKernelGGL(pw_wgrad256_kernel, dim3((cout / 256) * ((cin + 255) / 256), S), dim3(512), 0, st,
-                       x, grad_y, b, cin, cout, n, S, (float*)ws);
+  const PwWgradPlan p = pw_wgrad_plan(b, cin, cout, n);
+  PCFM_CHECK_ARG(ws_bytes >= p.part_bytes, "pointwise_wgrad: workspace %zu < %zu bytes", ws_bytes,
+                 p.part_bytes);
+  if (p.wide) {
+    hipLaunchKernelGGL(pw_wgrad256_kernel, dim3(p.tiles, p.splits), dim3(512), 0, st, x, grad_y, b,
+                       cin, cout, n, p.splits, (float*)ws);
   } else {
-    const int tiles = ((cout + 127) / 128) * ((cin + 127) / 128);
-    hipLaunchKernelGGL(pw_wgrad_kernel, dim3(tiles, S), dim3(256), 0, st, x, grad_y, b, cin,
-                       cout, n, S, (float*)ws);
+    hipLaunchKernelGGL(pw_wgrad_kernel, dim3(p.tiles, p.splits), dim3(256), 0, st, x, grad_y, b,
+                       cin, cout, n, p.splits, (float*)ws);
   }
   hipLaunchKernelGGL(pw_wgrad_reduce_kernel, dim3(ceil_div((long long)total, 64)), dim3(256), 0,
-                     st, (const float*)ws, total, S, grad_w);
+                     st, (const float*)ws, total, p.splits, grad_w);
   return check_launch("pointwise_wgrad");
 }
 
 extern "C" size_t pcfm_pointwise_wgrad_workspace_bytes(int b, int cin, int cout, int n) {
   if (!pw_ok(b, cin, cout, n) || b == 0 || n == 0) return 0;
-  return (size_t)pw_wgrad_splits(b, cin, cout, n) * cout * cin * sizeof(float);
+  return pw_wgrad_plan(b, cin, cout, n).part_bytes;
 }
 
 extern "C" int pcfm_pointwise_wgrad(const float* x, const float* grad_y, int b, int cin, int cout,
@@ -1226,9 +1021,7 @@ extern "C" int pcfm_pointwise_wgrad(const float* x, const float* grad_y, int b, 
     }
     return PCFM_OK;
   }
-  const size_t need = pcfm_pointwise_wgrad_workspace_bytes(b, cin, cout, n);
-  PCFM_CHECK_ARG(ws_bytes >= need, "pointwise_wgrad: workspace %zu < %zu bytes", ws_bytes, need);
-  return pw_wgrad_launch(one_part(x, cin), grad_y, b, cin, cout, n, grad_w, ws, st);
+  return pw_wgrad_launch(one_part(x, cin), grad_y, b, cin, cout, n, grad_w, ws, ws_bytes, st);
 }
 
 extern "C" int pcfm_pointwise_wgrad_parts(int nx, const float* const* x, const int* xw,
@@ -1240,8 +1033,5 @@ extern "C" int pcfm_pointwise_wgrad_parts(int nx, const float* const* x, const i
                  "pointwise_wgrad_parts: bad input parts (1..%d)", kMaxParts);
   PCFM_CHECK_ARG(pw_ok(b, cin, cout, n) && b > 0 && n > 0,
                  "pointwise_wgrad_parts: bad shape b=%d cin=%d cout=%d n=%d", b, cin, cout, n);
-  const size_t need = pcfm_pointwise_wgrad_workspace_bytes(b, cin, cout, n);
-  PCFM_CHECK_ARG(ws_bytes >= need, "pointwise_wgrad_parts: workspace %zu < %zu bytes", ws_bytes,
-                 need);
-  return pw_wgrad_launch(px, grad_y, b, cin, cout, n, grad_w, ws, (hipStream_t)stream);
+  return pw_wgrad_launch(px, grad_y, b, cin, cout, n, grad_w, ws, ws_bytes, (hipStream_t)stream);
 }

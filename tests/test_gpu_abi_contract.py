@@ -18,7 +18,7 @@ only the Chamfer backward does (the scatters sort), every other output of every
 row compares exactly.
 
 A row's id names the kernel form its shape takes, read from the dispatch code
-(plan_gather in csrc/rows.hpp, pw_path / pw_wgrad_splits in csrc/pointwise.hip,
+(plan_gather in csrc/rows.hpp, pw_plan / pw_wgrad_plan in csrc/pointwise.hip,
 conv3_wgrad_splits, glds_splits and the list choice in csrc/conv3d.hip).
 """
 import contextlib

@@ -26,7 +26,13 @@ def ops():
                                           # streaming form (M <= 128, K <= 256, multiples of 32):
                                           # ragged point tiles, 8 K-chunks in the backward-data
                                           (2, 128, 256, 1000), (1, 96, 32, 45),
-                                          (8, 128, 128, 20000)])
+                                          (8, 128, 128, 20000),
+                                          # the 128-row tile forward, ragged K and ragged N
+                                          (4, 262, 128, 16385),
+                                          # the wide (256 x 256 tile) weight gradient: a scalar
+                                          # tail step; n % 4 != 0 with two input-channel tiles
+                                          # (and the 64-row tile forward at K = 512)
+                                          (2, 256, 256, 100), (1, 512, 256, 77)])
 def test_pointwise_vs_fp64(ops, b, cin, cout, n):
     g = torch.Generator(device="cuda").manual_seed(cin * 7 + cout + n)
     x = torch.randn(b, cin, n, device="cuda", generator=g)
@@ -166,16 +172,28 @@ def test_context_stem_fold_matches_concat(ops, monkeypatch):
     assert _rel(o1, o0.double().cpu()) < 1e-4
 
 
-@pytest.mark.parametrize("b,cin,cout,n", [(8, 256, 256, 20000), (8, 128, 256, 20000),
-                                          (8, 256, 128, 20000),  # backward-data: M = cin = 256
-                                          (5, 200, 256, 16388),  # channel tail, ragged tile
-                                          (16, 64, 256, 4100)])  # one K-step, more tiles than CUs
+# the statistics group size each case must report: 64 points from the 256-row
+# tile, 32 from the streaming form
+STATS_GROUP = {
+    (8, 256, 256, 20000): 64, (8, 128, 256, 20000): 64,
+    (8, 256, 128, 20000): 32,  # backward-data: M = cin = 256 (forward: the streaming form)
+    (5, 200, 256, 16388): 64,  # channel tail, ragged tile
+    (16, 64, 256, 4100): 64,   # one K-step, more tiles than CUs
+    # the streaming form (pw_stream128_kernel):
+    (1, 96, 32, 45): 32,       # 32 output rows, a 13-point last group
+    (2, 128, 128, 64): 32,
+    (3, 256, 64, 129): 32,     # eight K-chunks, a one-point last group (centred sum 0)
+}
+
+
+@pytest.mark.parametrize("b,cin,cout,n", list(STATS_GROUP))
 def test_pointwise_256_row_shapes(ops, b, cin, cout, n):
     """The 256-row tile (pw_gemm256_kernel) over shapes with a channel tail, a
-    ragged point tile and one K-step: forward against fp64, the BatchNorm group
-    statistics present for the 256-row output, backward-data through the same
-    path.  (Its persistent LDS-DMA twin, bit-identical here in round 5 and
-    slower, was removed in round 6.)"""
+    ragged point tile and one K-step, and the streaming form: forward against
+    fp64, the BatchNorm group statistics present with the form's group size
+    (64 / 32 points) and checked against fp64, backward-data through the same
+    path.  (The 256-row tile's persistent LDS-DMA twin, bit-identical here in
+    round 5 and slower, was removed in round 6.)"""
     g = torch.Generator(device="cuda").manual_seed(b + cin + cout + n)
     x = torch.randn(b, cin, n, device="cuda", generator=g)
     w = torch.randn(cout, cin, 1, device="cuda", generator=g) / cin ** 0.5
@@ -183,12 +201,13 @@ def test_pointwise_256_row_shapes(ops, b, cin, cout, n):
     gy = torch.randn(b, cout, n, device="cuda", generator=g)
     y = ops.pointwise_forward(x, w, bias)
     fs = ops.pointwise_forward_bnstats(x, w, bias)
-    assert fs is not None or cout != 256
-    if fs is not None:  # per (channel, 64-point group): the group's mean and centred sum of squares
+    assert fs is not None
+    if fs is not None:  # per (channel, point group): the group's mean and centred sum of squares
         assert torch.equal(fs[0], y)
         st = fs[1]
-        ng = st.shape[1] // b
-        G = (n + ng - 1) // ng
+        group = STATS_GROUP[(b, cin, cout, n)]
+        assert st.shape == (cout, b * ((n + group - 1) // group), 2)
+        ng, G = st.shape[1] // b, group  # (not ceil(n / ng): that is 23 for n = 45 in 2 groups)
         yd = torch.nn.functional.pad(y.double(), (0, ng * G - n)).view(b, cout, ng, G)
         cnt = torch.full((ng,), float(G), device="cuda", dtype=torch.float64)
         cnt[-1] = n - (ng - 1) * G

@@ -2,8 +2,7 @@
 set -e
 V=point-cloud-flow-matching_amd/csrc/build/variants
 OUT=gpurun_out/pw_dec.jsonl
-PCFM_PW_GLDS=0 timeout -k 10 120 python tools/pw_ab.py staged > $OUT
-timeout -k 10 120 python tools/pw_ab.py glds >> $OUT
+timeout -k 10 120 python tools/pw_ab.py main > $OUT
 for n in "$@"; do
   PCFM_LIB=$V/libpcfm_$n.so timeout -k 10 120 python tools/pw_ab.py $n >> $OUT
 done

@@ -1,7 +1,7 @@
 """Kernel-only timing of the pointwise GEMM forms at the C2 shapes (dev tool):
 the weight image is prepared once and only pcfm_pointwise_gemm is timed, with
-HIP events around 50 back-to-back launches.  PCFM_PW_WST=0/1 picks the 256-row
-tile / the weight-stationary form; PCFM_LIB=<variant> loads a measurement build.
+HIP events around 50 back-to-back launches.  PCFM_LIB=<variant> loads a
+measurement build.
 One JSON line: python tools/pw_kernel_ab.py TAG"""
 import json
 import os
@@ -13,7 +13,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "point-cloud-flow-matching_amd")]
 from pcfm import _lib, ops  # noqa: E402
 
-res = {"tag": sys.argv[1] if len(sys.argv) > 1 else "main", "wst": os.environ.get("PCFM_PW_WST", "1")}
+res = {"tag": sys.argv[1] if len(sys.argv) > 1 else "main"}
 g = torch.Generator(device="cuda").manual_seed(0)
 for b, ci, co, n in ((8, 256, 256, 20000), (8, 128, 256, 20000)):
     x = torch.randn(b, ci, n, device="cuda", generator=g)
