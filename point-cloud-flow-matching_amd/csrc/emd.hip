@@ -20,28 +20,41 @@
 //     and order as the reference's `match += w` (:143-144), with 1/10th of the
 //     HBM traffic.
 //   * exp is the hardware exp2 on x*log2(e): the reference is built with
-//     --use_fast_math (__expf, backend.py:20), so EMD parity is tolerance-based.
+//     --use_fast_math (__expf, backend.py:20), so EMD parity is tolerance-based
+//     (tests/helpers/emd_ref.py is the fp64 reference of what is defined here).
+//
+// Measured history (B = 8, N = 2048, MI355X): the round-3 split form (6 launches
+// per level, S-way partials reduced by separate finalize kernels; it can be
+// built at the commit before this file lost it) 0.67 ms; a form with the
+// finalizes folded into the next pass, each block re-reducing the S partials
+// of its columns, 0.80 ms (the serial partial reads sat in front of every
+// pass); the round-3 cooperative one-launch form with cooperative_groups grid
+// barriers 4.45 ms (a grid.sync() costs ~0.1 us per block on ROCm 7.2, ~100 us
+// at 1024 blocks, against ~1.7 us for a kernel boundary); the row passes as 30
+// separate launches with scalar-loaded columns 0.51 ms, with LDS-staged columns
+// and the fused cost 0.39 ms.
 #include "pcfm_common.hpp"
 
 #include <algorithm>
 #include <cstdlib>
+#include <initializer_list>
+#include <utility>
 
 namespace pcfm {
 namespace {
 
 constexpr int kLevels = 10;
 // level_j = -4^j for j = 7 .. -1, then 0 (emd_kernel.cu:44-48).
-__constant__ float c_levels[kLevels] = {-16384.0f, -4096.0f, -1024.0f, -256.0f, -64.0f,
-                                        -16.0f,    -4.0f,    -1.0f,    -0.25f,  0.0f};
 constexpr float h_levels[kLevels] = {-16384.0f, -4096.0f, -1024.0f, -256.0f, -64.0f,
                                      -16.0f,    -4.0f,    -1.0f,    -0.25f,  0.0f};
+// level_j * log2(e) in one float factor.  level_j is a power of two, so
+// d2 * (level_j * log2 e) rounds exactly as (level_j * d2) * log2 e.
+constexpr float level_log2e(int j) { return h_levels[j] * 1.4426950408889634f; }
 
-__device__ __forceinline__ float fast_expf(float x) {
-  return __builtin_amdgcn_exp2f(x * 1.4426950408889634f);
-}
+// exp(level * d2) as the hardware exp2 of float(d2) * lvl2, lvl2 = level * log2(e)
 template <typename T>
-__device__ __forceinline__ T emd_exp(T x) {
-  return (T)fast_expf((float)x);
+__device__ __forceinline__ T emd_exp2(T d2, T lvl2) {
+  return (T)__builtin_amdgcn_exp2f((float)d2 * (float)lvl2);
 }
 
 template <typename T>
@@ -57,39 +70,29 @@ __device__ __forceinline__ double fmaT<double>(double a, double b, double c) {
 
 constexpr int kThreads = 256;
 
-// MODE 0: acc += e * coef[c]            (pass 1: coef = remainR, :70-76)
-// MODE 1: acc += e * coef[c]            (pass 2: coef = ratioL,  :102-107)
-// MODE 2: acc += (e * rowscale[i]) * coef[c]  (pass 3: ratioL[k] * ratioR[l], :139-146)
-// grid = (row blocks, S, b); part[s][b*nr + i].
-template <typename T, int MODE>
-__global__ void __launch_bounds__(kThreads)
-    emd_pass_kernel(const T* __restrict__ rows, int nr, const T* __restrict__ cols, int ncol,
-                    int b, T level, const T* __restrict__ coef, const T* __restrict__ rowscale,
-                    int S, T* __restrict__ part) {
-  const int bb = blockIdx.z;
-  const int s = blockIdx.y;
-  const int i = blockIdx.x * kThreads + threadIdx.x;
+// Row i of batch element bb, clamped to the element's last row: a lane past
+// the end loads a valid row unconditionally and its result is never stored.
+__device__ __forceinline__ size_t row_at(int bb, int nr, int i) {
   const int ii = i < nr ? i : nr - 1;
-  const T* rp = rows + ((size_t)bb * nr + ii) * 3;
-  const T x1 = rp[0], y1 = rp[1], z1 = rp[2];
-  T rl = (T)0;
-  if constexpr (MODE == 2) rl = rowscale[(size_t)bb * nr + ii];
-  const int c0 = (int)(((long long)ncol * s) / S);
-  const int c1 = (int)(((long long)ncol * (s + 1)) / S);
-  const T* __restrict__ cb = cols + (size_t)bb * ncol * 3;
-  const T* __restrict__ kb = coef + (size_t)bb * ncol;
-  T acc = 0;
-#pragma unroll 4
-  for (int c = c0; c < c1; ++c) {
-    const T d2 = sqdist3(cb[3 * c] - x1, cb[3 * c + 1] - y1, cb[3 * c + 2] - z1);
-    const T e = emd_exp<T>(level * d2);
-    if constexpr (MODE == 2) {
-      acc = fmaT<T>(e * rl, kb[c], acc);
-    } else {
-      acc = fmaT<T>(e, kb[c], acc);
-    }
-  }
-  if (i < nr) part[(size_t)s * b * nr + (size_t)bb * nr + i] = acc;
+  return (size_t)bb * nr + ii;
+}
+
+// The finalize expressions of a level; fminf / fmaxf take float arguments in
+// the reference for both dtypes.
+// ratioL = remainL / (1e-9 + suml)    (:57, :81)
+template <typename T>
+__device__ __forceinline__ T emd_ratio_l(T remL, T suml) {
+  return remL / ((T)1e-9f + suml);
+}
+// consumption = min(remainR / (sumr + 1e-9), 1); ratioR = consumption * remainR   (:111-115)
+template <typename T>
+__device__ __forceinline__ T emd_ratio_r(T remR, T sumr) {
+  return (T)fminf((float)(remR / (sumr + (T)1e-9f)), 1.0f) * remR;
+}
+// remain = max(0, remain - sum): remainR (:116) and remainL (:150)
+template <typename T>
+__device__ __forceinline__ T emd_remain(T rem, T sum) {
+  return (T)fmaxf(0.0f, (float)(rem - sum));
 }
 
 template <typename T>
@@ -97,85 +100,6 @@ __device__ __forceinline__ T sum_parts(const T* part, int S, size_t stride, size
   T v = 0;
   for (int s = 0; s < S; ++s) v += part[(size_t)s * stride + i];
   return v;
-}
-
-template <typename T>
-__global__ void emd_init_kernel(T* remL, size_t nl, T multiL, T* remR, size_t nr, T multiR) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < nl) remL[i] = multiL;
-  if (i < nr) remR[i] = multiR;
-}
-
-// ratioL = remainL / (1e-9 + suml)    (:57, :81)
-template <typename T>
-__global__ void emd_fin1_kernel(const T* __restrict__ part, int S, size_t total,
-                                const T* __restrict__ remL, T* __restrict__ ratL) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  ratL[i] = remL[i] / ((T)1e-9f + sum_parts(part, S, total, i));
-}
-
-// sumr *= remainR; consumption = min(remainR / (sumr + 1e-9), 1);
-// ratioR = consumption * remainR; remainR = max(0, remainR - sumr)   (:111-116)
-// fminf/fmaxf take float arguments in the reference for both dtypes.
-template <typename T>
-__global__ void emd_fin2_kernel(const T* __restrict__ part, int S, size_t total,
-                                T* __restrict__ remR, T* __restrict__ ratR,
-                                T* __restrict__ levR) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  const T r = remR[i];
-  T sumr = sum_parts(part, S, total, i);
-  sumr *= r;
-  const T cons = (T)fminf((float)(r / (sumr + (T)1e-9f)), 1.0f);
-  const T rat = cons * r;
-  ratR[i] = rat;
-  levR[i] = rat;
-  remR[i] = (T)fmaxf(0.0f, (float)(r - sumr));
-}
-
-// remainL = max(0, remainL - suml); keep this level's ratioL   (:150-151)
-template <typename T>
-__global__ void emd_fin3_kernel(const T* __restrict__ part, int S, size_t total,
-                                T* __restrict__ remL, const T* __restrict__ ratL,
-                                T* __restrict__ levL) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= total) return;
-  remL[i] = (T)fmaxf(0.0f, (float)(remL[i] - sum_parts(part, S, total, i)));
-  levL[i] = ratL[i];
-}
-
-// match[b, l, k] = sum_j (exp(level_j * d2(k,l)) * ratioL_j[k]) * ratioR_j[l].
-// grid = (k blocks, l blocks of kLPer, b); lanes over k -> coalesced rows.
-constexpr int kLPer = 8;
-template <typename T>
-__global__ void __launch_bounds__(kThreads)
-    emd_match_kernel(const T* __restrict__ xyz1, const T* __restrict__ xyz2, int b, int n, int m,
-                     const T* __restrict__ levL, const T* __restrict__ levR,
-                     T* __restrict__ match) {
-  const int bb = blockIdx.z;
-  const int k = blockIdx.x * kThreads + threadIdx.x;
-  if (blockIdx.x * kThreads >= n) return;
-  const int kk = k < n ? k : n - 1;
-  const T* p1 = xyz1 + ((size_t)bb * n + kk) * 3;
-  const T x1 = p1[0], y1 = p1[1], z1 = p1[2];
-  T rl[kLevels];
-#pragma unroll
-  for (int j = 0; j < kLevels; ++j) rl[j] = levL[(size_t)j * b * n + (size_t)bb * n + kk];
-  const int l0 = blockIdx.y * kLPer;
-  const int l1 = min(m, l0 + kLPer);
-  for (int l = l0; l < l1; ++l) {
-    const T* p2 = xyz2 + ((size_t)bb * m + l) * 3;
-    const T d2 = sqdist3(p2[0] - x1, p2[1] - y1, p2[2] - z1);
-    T acc = 0;
-#pragma unroll
-    for (int j = 0; j < kLevels; ++j) {
-      const T rr = levR[(size_t)j * b * m + (size_t)bb * m + l];
-      const T e = emd_exp<T>((T)c_levels[j] * d2);
-      acc += (e * rl[j]) * rr;
-    }
-    if (k < n) match[((size_t)bb * m + l) * n + k] = acc;
-  }
 }
 
 template <typename T>
@@ -201,8 +125,7 @@ __global__ void __launch_bounds__(kThreads)
   __shared__ T red[kThreads / 64];
   const int bb = blockIdx.z, s = blockIdx.y;
   const int k = blockIdx.x * kThreads + threadIdx.x;
-  const int kk = k < n ? k : n - 1;
-  const T* p1 = xyz1 + ((size_t)bb * n + kk) * 3;
+  const T* p1 = xyz1 + row_at(bb, n, k) * 3;
   const T x1 = p1[0], y1 = p1[1], z1 = p1[2];
   const int l0 = (int)(((long long)m * s) / S), l1 = (int)(((long long)m * (s + 1)) / S);
   const T* __restrict__ cb = xyz2 + (size_t)bb * m * 3;
@@ -232,7 +155,8 @@ __global__ void __launch_bounds__(64)
 }
 
 // The match write with matchcost fused (the fused forward, pcfm_emd_approxmatch_cost_*):
-// match[b, l, k] as emd_match_kernel (skipped when match == nullptr), and per
+// match[b, l, k] = sum_j (exp(level_j * d2(k,l)) * ratioL_j[k]) * ratioR_j[l]
+// in level order (skipped when match == nullptr), and per
 // block the partial sum over its entries of d2 * match -- matchcost's terms
 // (emd_kernel.cu:199-241) -- to part[(bb * lblocks + lb) * kblocks + kb], so
 // the 4-byte-per-entry match matrix is not read back for the cost.  A block
@@ -249,18 +173,17 @@ __global__ void __launch_bounds__(kThreads)
   __shared__ T red[kThreads / 64];
   const int bb = blockIdx.z, kb = blockIdx.x, lb = blockIdx.y;
   const int k = kb * kThreads + threadIdx.x;
-  const int kk = k < n ? k : n - 1;
   const int l0 = lb * kMatchL, nl = min(kMatchL, m - l0);
   for (int e = threadIdx.x; e < nl * kW; e += kThreads) {
     const int li = e / kW, q = e - li * kW;
     sl[e] = q < kLevels ? levR[(size_t)q * b * m + (size_t)bb * m + l0 + li]
                         : xyz2[((size_t)bb * m + l0 + li) * 3 + (q - kLevels)];
   }
-  const T* p1 = xyz1 + ((size_t)bb * n + kk) * 3;
+  const T* p1 = xyz1 + row_at(bb, n, k) * 3;
   const T x1 = p1[0], y1 = p1[1], z1 = p1[2];
   T rl[kLevels];
 #pragma unroll
-  for (int j = 0; j < kLevels; ++j) rl[j] = levL[(size_t)j * b * n + (size_t)bb * n + kk];
+  for (int j = 0; j < kLevels; ++j) rl[j] = levL[(size_t)j * b * n + row_at(bb, n, k)];
   __syncthreads();
   T csum = 0;
   T* mrow = match != nullptr ? match + ((size_t)bb * m + l0) * n + k : nullptr;
@@ -270,10 +193,7 @@ __global__ void __launch_bounds__(kThreads)
     T acc = 0;
 #pragma unroll
     for (int j = 0; j < kLevels; ++j) {
-      // level_j * log2(e) in one float factor (exact: level_j is a power of two)
-      const T e = j == kLevels - 1 ? (T)1
-                                   : (T)__builtin_amdgcn_exp2f((float)d2 *
-                                                               (h_levels[j] * 1.4426950408889634f));
+      const T e = j == kLevels - 1 ? (T)1 : emd_exp2<T>(d2, (T)level_log2e(j));  // level 0: 1
       acc += (e * rl[j]) * q[j];
     }
     if (mrow != nullptr && k < n) mrow[(size_t)li * n] = acc;
@@ -292,7 +212,7 @@ __global__ void __launch_bounds__(kThreads)
   const int bb = blockIdx.z, s = blockIdx.y;
   const int k = blockIdx.x * kThreads + threadIdx.x;
   if (k >= n) return;
-  const T* p1 = xyz1 + ((size_t)bb * n + k) * 3;
+  const T* p1 = xyz1 + row_at(bb, n, k) * 3;
   const T x1 = p1[0], y1 = p1[1], z1 = p1[2];
   const int l0 = (int)(((long long)m * s) / S), l1 = (int)(((long long)m * (s + 1)) / S);
   const T* __restrict__ cb = xyz2 + (size_t)bb * m * 3;
@@ -350,75 +270,11 @@ __global__ void __launch_bounds__(kThreads)
   }
 }
 
-int emd_splits(int b, int n, int m) {
-  const long long rows = (long long)b * std::max(n, m);
-  const long long want_lanes = 4LL * kCUs * 4 * 64;  // ~4 waves per SIMD
-  int s = (int)std::max(1LL, (want_lanes + rows - 1) / std::max(1LL, rows));
-  s = std::min(s, std::max(1, std::min(n, m) / 64));
-  return std::max(1, std::min(s, 32));
-}
-
-template <typename T>
-struct EmdWs {
-  T *remL, *remR, *ratL, *ratR, *levL, *levR, *part;
-};
-
-size_t emd_ws_elems(int b, int n, int m) {
-  const size_t bn = (size_t)b * n, bm = (size_t)b * m;
-  const int S = emd_splits(b, n, m);
-  // the partials of the split form / the row-pass form's point packs (4 (bn + 2 bm));
-  // the region starts at 12 (bn + bm) elements: 16-B aligned for f32, 32-B for f64
-  const size_t part = std::max({(size_t)S * b * std::max(n, m) * 3,
-                                (size_t)b * S * ceil_div(std::max(n, 1), kThreads),
-                                4 * (bn + 2 * bm) +
-                                    (size_t)b * ceil_div(std::max(m, 1), kMatchL) *
-                                        ceil_div(std::max(n, 1), kThreads)});
-  return 2 * (bn + bm) + kLevels * (bn + bm) + part;
-}
-
-template <typename T>
-EmdWs<T> carve(void* ws, int b, int n, int m) {
-  const size_t bn = (size_t)b * n, bm = (size_t)b * m;
-  T* p = (T*)ws;
-  EmdWs<T> w;
-  w.remL = p;
-  p += bn;
-  w.remR = p;
-  p += bm;
-  w.ratL = p;
-  p += bn;
-  w.ratR = p;
-  p += bm;
-  w.levL = p;
-  p += kLevels * bn;
-  w.levR = p;
-  p += kLevels * bm;
-  w.part = p;
-  return w;
-}
-
-inline dim3 grid1d(size_t total, int threads = 256) {
-  return dim3(ceil_div((long long)std::max<size_t>(total, 1), threads));
-}
-
 // ---------------------------------------------------------------------------
-// Row-pass form (the default): ONE launch per pass of each level, its finalize
-// included, and no partial-sum buffer.  A block owns 64 rows (one per lane)
-// and splits the column range over its 16 waves; the 16 wave sums of a row
-// are added in wave order in LDS and the row's finalize (fin1 / fin2 / fin3
-// of the split form) runs right there, so the next pass reads finished
-// coefficients.  A level's third pass and the next level's first pass walk
-// the same (row k, column l) pairs, so they share one launch and one d2 per
-// pair: 21 pass launches + the pack + the match write (with the cost fused).
-// Measured history (B = 8, N = 2048, MI355X): the split form below (6 launches
-// per level, S-way partials reduced by separate finalize kernels) 0.67 ms; a
-// form with the finalizes folded into the next pass, each block re-reducing
-// the S partials of its columns, 0.80 ms (the serial partial reads sat in front
-// of every pass); the round-3 cooperative one-launch form with
-// cooperative_groups grid barriers 4.45 ms (a grid.sync() costs ~0.1 us per
-// block on ROCm 7.2, ~100 us at 1024 blocks, against ~1.7 us for a kernel
-// boundary); this form with 30 separate pass launches and scalar-loaded
-// columns 0.51 ms, with LDS-staged columns and the fused cost 0.39 ms.
+// The row passes: ONE launch per pass of each level, its finalize included,
+// and no partial-sum buffer.  A level's third pass and the next level's first
+// pass walk the same (row k, column l) pairs, so they share one launch and one
+// d2 per pair: 21 pass launches + the pack + the match write (with the cost fused).
 // ---------------------------------------------------------------------------
 constexpr int kRowWaves = 16;  // column splits per block, one wave each
 
@@ -464,15 +320,6 @@ __global__ void emd_pack_kernel(const T* __restrict__ xyz1, size_t bn, T multiL,
   }
 }
 
-// PH 0: rows k (packK), cols packL0 (coef remR);  suml -> ratL = remL / (1e-9 + suml)  (:57-81)
-// PH 1: rows l (packL0), cols packK (coef ratL);  sumr -> ratR, levR[lvl], remR (fin2) (:86-116)
-// PH 2: rows k (packK, row scale ratL), cols packL1 (coef ratR);  -> remL, levL[lvl]   (:119-151)
-// grid = (ceil(nr / 64), b), 1024 threads.  Each wave stages its column slice
-// through a wave-private LDS chunk (one 16-B load per lane and column pair,
-// the next chunk's loads in flight while this one is used); the column loop
-// then reads a column as one broadcast ds_read, whose in-order completion
-// lets the compiler keep several in flight (scalar loads of the columns
-// complete out of order, so every use waited for all of them: 13.8 us/pass).
 constexpr int kColChunk = 128;  // columns per wave per LDS chunk (64 for PH 3: two packs)
 
 template <typename T, int PH>
@@ -487,9 +334,7 @@ __device__ __forceinline__ T rowpass_chunk(const Col4<T>* __restrict__ st, int c
   for (int c = 0; c < cnt; ++c) {
     const Col4<T> q = st[c];
     const T d2 = sqdist3(q.x - x1, q.y - y1, q.z - z1);
-    // level * log2(e) folded into one float factor: level is -4^j, a power of
-    // two, so d2 * (level * log2 e) rounds exactly as emd_exp's (level * d2) * log2 e
-    const T e = (T)__builtin_amdgcn_exp2f((float)d2 * (float)lvl2);
+    const T e = emd_exp2<T>(d2, lvl2);
     if constexpr (PH == 2) {
       acc = fmaT<T>(e * rl, q.w, acc);
     } else {
@@ -508,16 +353,16 @@ __device__ __forceinline__ void rowpass_pair(const Col4<T>* __restrict__ st, int
   for (int c = 0; c < cnt; ++c) {
     const Col4<T> q = st[c];
     const T rr = st[64 + c].w;
-    const float d2 = (float)sqdist3(q.x - x1, q.y - y1, q.z - z1);
-    const T e2 = (T)__builtin_amdgcn_exp2f(d2 * (float)lvl2);
-    const T e0 = (T)__builtin_amdgcn_exp2f(d2 * (float)lvl2b);
+    const T d2 = sqdist3(q.x - x1, q.y - y1, q.z - z1);
+    const T e2 = emd_exp2<T>(d2, lvl2);
+    const T e0 = emd_exp2<T>(d2, lvl2b);
     acc2 = fmaT<T>(e2 * rl, q.w, acc2);
     acc0 = fmaT<T>(e0, rr, acc0);
   }
 }
 
 // PH 0: rows k (packK), cols packL0 (coef remR);  suml -> ratL = remL / (1e-9 + suml)  (:57-81)
-// PH 1: rows l (packL0), cols packK (coef ratL);  sumr -> ratR, levR[lvl], remR (fin2) (:86-116)
+// PH 1: rows l (packL0), cols packK (coef ratL);  sumr -> ratR, levR[lvl], remR        (:86-116)
 // PH 2: rows k (packK, row scale ratL), cols packL1 (coef ratR);  -> remL, levL[lvl]   (:119-151)
 // PH 3: PH 2 of level lvl then PH 0 of level lvl+1 (lvl2b), one launch: the
 //       column sums of both are taken in the same order as the two launches,
@@ -540,8 +385,7 @@ __global__ void __launch_bounds__(64 * kRowWaves)
   const int bb = blockIdx.y, lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int i = blockIdx.x * 64 + lane;
-  const int ii = i < nr ? i : nr - 1;
-  const Col4<T> rp = rows[(size_t)bb * nr + ii];
+  const Col4<T> rp = rows[row_at(bb, nr, i)];
   const T rl = rp.w;  // PH 2 / 3: ratL of the row
   const int c0 = (int)(((long long)ncol * w) / kRowWaves);
   const int c1 = (int)(((long long)ncol * (w + 1)) / kRowWaves);
@@ -582,53 +426,141 @@ __global__ void __launch_bounds__(64 * kRowWaves)
   const size_t idx = (size_t)bb * nr + i;
   const size_t lv = (size_t)lvl * gridDim.y * nr + idx;
   if constexpr (PH == 0) {
-    rows[idx].w = s.remL[idx] / ((T)1e-9f + t);
+    rows[idx].w = emd_ratio_l(s.remL[idx], t);
   } else if constexpr (PH == 1) {
     const T r = rp.w;
-    const T sumr = t * r;
-    const T cons = (T)fminf((float)(r / (sumr + (T)1e-9f)), 1.0f);
-    const T rat = cons * r;
+    const T sumr = t * r;  // sumr *= remainR (:111)
+    const T rat = emd_ratio_r(r, sumr);
     s.packL1[idx].w = rat;
     s.levR[lv] = rat;
-    rows[idx].w = (T)fmaxf(0.0f, (float)(r - sumr));
-  } else if constexpr (PH == 2) {
-    s.remL[idx] = (T)fmaxf(0.0f, (float)(s.remL[idx] - t));
-    s.levL[lv] = rl;
-  } else {
-    const T rem = (T)fmaxf(0.0f, (float)(s.remL[idx] - t2));  // level lvl's fin3
+    rows[idx].w = emd_remain(r, sumr);
+  } else {  // PH 2, and PH 3: level lvl's remainL, then level lvl+1's ratioL
+    const T rem = emd_remain(s.remL[idx], PH == 3 ? t2 : t);
     s.remL[idx] = rem;
     s.levL[lv] = rl;
-    rows[idx].w = rem / ((T)1e-9f + t);  // level lvl+1's ratL
+    if constexpr (PH == 3) rows[idx].w = emd_ratio_l(rem, t);
   }
 }
 
-// PCFM_EMD_FORM=split: every pass and finalize its own launch, S-way partials
-// (measurement / the cross-form test); =unfused: the row-pass form with PH 2
-// and the next level's PH 0 as separate launches; default: the fused row-pass form
-bool emd_split_form() {
-  const char* e = std::getenv("PCFM_EMD_FORM");
-  return e != nullptr && e[0] == 's';
+// ---------------------------------------------------------------------------
+// Host side: one plan of the workspace, one prologue, four entries.
+// ---------------------------------------------------------------------------
+// Column splits of matchcost's and matchcost_bwd's partials: ~4 waves per SIMD.
+constexpr int emd_splits(int b, int n, int m) {
+  const long long rows = (long long)b * std::max(n, m);
+  const long long want_lanes = 4LL * kCUs * 4 * 64;
+  int s = (int)std::max(1LL, (want_lanes + rows - 1) / std::max(1LL, rows));
+  s = std::min(s, std::max(1, std::min(n, m) / 64));
+  return std::max(1, std::min(s, 32));
 }
-bool emd_unfused_form() {
-  const char* e = std::getenv("PCFM_EMD_FORM");
-  return e != nullptr && e[0] == 'u';
+constexpr size_t blocks_of(int count, int per) {
+  return (size_t)((std::max(count, 1) + per - 1) / per);
 }
 
-// match (when non-null) and, when cost is non-null, the fused matchcost.
+// The workspace of every pcfm_emd_* entry as offsets in elements of T.  The
+// regions of approxmatch follow one another, each starting where the one
+// before it ends.  The Col4 packs come first and each is a whole number of
+// Col4 (4 elements), so they are aligned whenever ws itself is aligned to
+// sizeof(Col4<T>) = 16 B (f32) / 32 B (f64), which every device allocation is
+// -- whatever else the workspace holds.  matchcost and matchcost_bwd use
+// nothing but their block partials, which therefore start at 0.
+static_assert(sizeof(Col4<float>) == 4 * sizeof(float) &&
+              sizeof(Col4<double>) == 4 * sizeof(double));
+struct EmdPlan {
+  int S = 1;  // emd_splits
+  size_t bn = 0, bm = 0;
+  size_t packK = 0, packL0 = 0, packL1 = 0;  // Col4 [bn], [bm], [bm]
+  size_t remL = 0;                           // [bn]
+  size_t levL = 0, levR = 0;                 // [kLevels][bn], [kLevels][bm]
+  size_t mpart = 0, mpart_elems = 0;         // emd_match_cost_kernel's block partials
+  size_t part = 0, part_elems = 0;           // emd_cost_kernel's / emd_grad1_kernel's partials
+  size_t total = 0, bytes = 0;
+
+  constexpr EmdPlan(int b, int n, int m, size_t elem_bytes)
+      : S(emd_splits(b, n, m)), bn((size_t)b * n), bm((size_t)b * m) {
+    const size_t kblocks = blocks_of(n, kThreads);
+    mpart_elems = b * blocks_of(m, kMatchL) * kblocks;
+    part_elems = std::max((size_t)b * S * kblocks, (size_t)S * bn * 3);
+    size_t end = 0;
+    for (auto [region, elems] : {std::pair<size_t*, size_t>{&packK, 4 * bn},
+                                 {&packL0, 4 * bm},
+                                 {&packL1, 4 * bm},
+                                 {&remL, bn},
+                                 {&levL, kLevels * bn},
+                                 {&levR, kLevels * bm},
+                                 {&mpart, mpart_elems}}) {
+      *region = end;
+      end += elems;
+    }
+    total = std::max(end, part + part_elems);
+    bytes = total * elem_bytes;
+  }
+};
+
+// the packs aligned, and the total the end of whichever region ends last
+constexpr bool emd_plan_ok() {
+  constexpr int sizes[] = {0, 1, 37, 64, 513, 2048, 20000};
+  for (int b : sizes)
+    for (int n : sizes)
+      for (int m : sizes)
+        for (size_t e : {(size_t)4, (size_t)8}) {
+          const EmdPlan p(b, n, m, e);
+          if (p.packK % 4 != 0 || p.packL0 % 4 != 0 || p.packL1 % 4 != 0) return false;
+          if (p.total != std::max(p.mpart + p.mpart_elems, p.part + p.part_elems)) return false;
+          if (p.bytes != p.total * e) return false;
+        }
+  return true;
+}
+static_assert(emd_plan_ok(), "EmdPlan: packs unaligned, or the total is not the last region's end");
+
 template <typename T>
-int approxmatch_rowpass(const T* xyz1, const T* xyz2, int b, int n, int m, T* match, T* cost,
-                        EmdWs<T> w, hipStream_t st) {
-  const size_t bn = (size_t)b * n, bm = (size_t)b * m;
-  Col4<T>* pk = reinterpret_cast<Col4<T>*>(w.part);  // 16/32-B aligned: see emd_ws_elems
-  EmdRowState<T> s{pk, pk + bn, pk + bn + bm, w.remL, w.levL, w.levR};
+using EmdOut = std::pair<T*, size_t>;  // an output and its element count
+
+// The prologue of the four entries: argument and workspace checks, then either
+// launch(plan, ws) or, for an empty problem, the outputs zero-filled.
+template <typename T, typename Launch>
+int emd_entry(const char* who, int b, int n, int m, void* ws, size_t ws_bytes, hipStream_t st,
+              std::initializer_list<EmdOut<T>> outs, Launch&& launch) {
+  PCFM_CHECK_ARG(b >= 0 && n >= 0 && m >= 0, "%s: negative size", who);
+  const EmdPlan p(b, n, m, sizeof(T));
+  PCFM_CHECK_ARG(ws_bytes >= p.bytes, "%s: workspace %zu < %zu bytes", who, ws_bytes, p.bytes);
+  if (b == 0) return PCFM_OK;
+  if (n != 0 && m != 0) {
+    launch(p, (T*)ws);
+    return check_launch(who);
+  }
+  for (const EmdOut<T>& o : outs) {
+    if (o.first == nullptr || o.second == 0) continue;
+    const hipError_t e = hipMemsetAsync(o.first, 0, o.second * sizeof(T), st);
+    if (e != hipSuccess) {
+      set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
+      return (int)e;
+    }
+  }
+  return PCFM_OK;
+}
+
+inline dim3 grid1d(size_t total, int threads = 256) {
+  return dim3(ceil_div((long long)std::max<size_t>(total, 1), threads));
+}
+
+// The 21 pass launches, then match (when non-null) and, when cost is non-null,
+// the fused matchcost.  PCFM_EMD_FORM=unfused runs PH 2 and the next level's
+// PH 0 as separate launches (31): what pins the fused PH 3 bit for bit.
+template <typename T>
+void launch_approxmatch(const T* xyz1, const T* xyz2, int b, int n, int m, T* match, T* cost,
+                        const EmdPlan& p, T* ws, hipStream_t st) {
+  auto pack = [ws](size_t at) { return reinterpret_cast<Col4<T>*>(ws + at); };
+  const EmdRowState<T> s{pack(p.packK), pack(p.packL0), pack(p.packL1),
+                         ws + p.remL,   ws + p.levL,    ws + p.levR};
   const T multiL = n >= m ? (T)1 : (T)(m / n);  // integer ratio of the cloud sizes (:27-33)
   const T multiR = n >= m ? (T)(n / m) : (T)1;
-  hipLaunchKernelGGL(emd_pack_kernel<T>, grid1d(std::max(bn, bm)), dim3(256), 0, st, xyz1, bn,
-                     multiL, xyz2, bm, multiR, s);
+  hipLaunchKernelGGL(emd_pack_kernel<T>, grid1d(std::max(p.bn, p.bm)), dim3(256), 0, st, xyz1,
+                     p.bn, multiL, xyz2, p.bm, multiR, s);
   const dim3 gL(ceil_div(n, 64), b), gR(ceil_div(m, 64), b), blk(64 * kRowWaves);
-  // level_j * log2(e), exact in float: level_j is a power of two
-  auto lv2 = [](int j) { return (T)(h_levels[j] * 1.4426950408889634f); };
-  const bool fused = !emd_unfused_form();
+  auto lv2 = [](int j) { return (T)level_log2e(j); };
+  const char* form = std::getenv("PCFM_EMD_FORM");
+  const bool fused = form == nullptr || form[0] != 'u';
   hipLaunchKernelGGL((emd_rowpass_kernel<T, 0>), gL, blk, 0, st, n, m, lv2(0), (T)0, 0, s);
   for (int j = 0; j < kLevels; ++j) {
     hipLaunchKernelGGL((emd_rowpass_kernel<T, 1>), gR, blk, 0, st, m, n, lv2(j), (T)0, j, s);
@@ -643,135 +575,59 @@ int approxmatch_rowpass(const T* xyz1, const T* xyz2, int b, int n, int m, T* ma
     }
   }
   const dim3 gm(ceil_div(n, kThreads), ceil_div(m, kMatchL), b);
-  T* cpart = w.part + 4 * (bn + 2 * bm);  // after the packs (emd_ws_elems)
   hipLaunchKernelGGL(emd_match_cost_kernel<T>, gm, dim3(kThreads), 0, st, xyz1, xyz2, b, n, m,
-                     (const T*)w.levL, (const T*)w.levR, match, cpart);
+                     (const T*)s.levL, (const T*)s.levR, match, ws + p.mpart);
   if (cost != nullptr)
-    hipLaunchKernelGGL(emd_cost_fin_kernel<T>, dim3(b), dim3(64), 0, st, (const T*)cpart,
+    hipLaunchKernelGGL(emd_cost_fin_kernel<T>, dim3(b), dim3(64), 0, st, (const T*)(ws + p.mpart),
                        (int)(gm.x * gm.y), cost);
-  return check_launch("approxmatch");
 }
 
 template <typename T>
 int approxmatch(const T* xyz1, const T* xyz2, int b, int n, int m, T* match, void* ws,
                 size_t ws_bytes, hipStream_t st) {
-  PCFM_CHECK_ARG(b >= 0 && n >= 0 && m >= 0, "approxmatch: negative size");
-  PCFM_CHECK_ARG(ws_bytes >= emd_ws_elems(b, n, m) * sizeof(T),
-                 "approxmatch: workspace %zu < %zu bytes", ws_bytes,
-                 emd_ws_elems(b, n, m) * sizeof(T));
-  if (b == 0 || n == 0 || m == 0) return PCFM_OK;
-  EmdWs<T> w = carve<T>(ws, b, n, m);
-  if (!emd_split_form()) return approxmatch_rowpass(xyz1, xyz2, b, n, m, match, (T*)nullptr, w, st);
-  const int S = emd_splits(b, n, m);
-  // multiL/multiR: integer ratio of the cloud sizes (:27-33)
-  const T multiL = n >= m ? (T)1 : (T)(m / n);
-  const T multiR = n >= m ? (T)(n / m) : (T)1;
-  const size_t bn = (size_t)b * n, bm = (size_t)b * m;
-  hipLaunchKernelGGL(emd_init_kernel<T>, grid1d(std::max(bn, bm)), dim3(256), 0, st, w.remL, bn,
-                     multiL, w.remR, bm, multiR);
-  const dim3 gL(ceil_div(n, kThreads), S, b), gR(ceil_div(m, kThreads), S, b);
-  for (int j = 0; j < kLevels; ++j) {
-    const T level = (T)h_levels[j];
-    // pass 1: rows = xyz1 (k), cols = xyz2 (l), coef = remainR
-    hipLaunchKernelGGL((emd_pass_kernel<T, 0>), gL, dim3(kThreads), 0, st, xyz1, n, xyz2, m, b,
-                       level, w.remR, (const T*)nullptr, S, w.part);
-    hipLaunchKernelGGL(emd_fin1_kernel<T>, grid1d(bn), dim3(256), 0, st, w.part, S, bn, w.remL,
-                       w.ratL);
-    // pass 2: rows = xyz2 (l), cols = xyz1 (k), coef = ratioL
-    hipLaunchKernelGGL((emd_pass_kernel<T, 1>), gR, dim3(kThreads), 0, st, xyz2, m, xyz1, n, b,
-                       level, w.ratL, (const T*)nullptr, S, w.part);
-    hipLaunchKernelGGL(emd_fin2_kernel<T>, grid1d(bm), dim3(256), 0, st, w.part, S, bm, w.remR,
-                       w.ratR, w.levR + (size_t)j * bm);
-    // pass 3: rows = xyz1 (k), cols = xyz2 (l), coef = ratioR, rowscale = ratioL
-    hipLaunchKernelGGL((emd_pass_kernel<T, 2>), gL, dim3(kThreads), 0, st, xyz1, n, xyz2, m, b,
-                       level, w.ratR, (const T*)w.ratL, S, w.part);
-    hipLaunchKernelGGL(emd_fin3_kernel<T>, grid1d(bn), dim3(256), 0, st, w.part, S, bn, w.remL,
-                       w.ratL, w.levL + (size_t)j * bn);
-  }
-  dim3 gm(ceil_div(n, kThreads), ceil_div(m, kLPer), b);
-  hipLaunchKernelGGL(emd_match_kernel<T>, gm, dim3(kThreads), 0, st, xyz1, xyz2, b, n, m, w.levL,
-                     w.levR, match);
-  return check_launch("approxmatch");
+  return emd_entry<T>("approxmatch", b, n, m, ws, ws_bytes, st, {}, [&](const EmdPlan& p, T* w) {
+    launch_approxmatch<T>(xyz1, xyz2, b, n, m, match, nullptr, p, w, st);
+  });
 }
 
-// approxmatch + matchcost in one call (row-pass form; the cost from the match
-// kernel's partials).  match may be null: the cost alone, match not written.
+// approxmatch + matchcost in one call (the cost from the match kernel's
+// partials).  match may be null: the cost alone, match not written.
 template <typename T>
 int approxmatch_cost(const T* xyz1, const T* xyz2, int b, int n, int m, T* match, T* cost,
                      void* ws, size_t ws_bytes, hipStream_t st) {
-  PCFM_CHECK_ARG(b >= 0 && n >= 0 && m >= 0, "approxmatch_cost: negative size");
   PCFM_CHECK_ARG(cost != nullptr, "approxmatch_cost: cost is required");
-  PCFM_CHECK_ARG(ws_bytes >= emd_ws_elems(b, n, m) * sizeof(T),
-                 "approxmatch_cost: workspace %zu < %zu bytes", ws_bytes,
-                 emd_ws_elems(b, n, m) * sizeof(T));
-  if (b == 0) return PCFM_OK;
-  if (n == 0 || m == 0) {
-    hipError_t e = hipMemsetAsync(cost, 0, (size_t)b * sizeof(T), st);
-    if (e == hipSuccess && match != nullptr)
-      e = hipMemsetAsync(match, 0, (size_t)b * n * m * sizeof(T), st);
-    if (e != hipSuccess) {
-      set_error("approxmatch_cost: hipMemsetAsync: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return PCFM_OK;
-  }
-  return approxmatch_rowpass(xyz1, xyz2, b, n, m, match, cost, carve<T>(ws, b, n, m), st);
+  return emd_entry<T>("approxmatch_cost", b, n, m, ws, ws_bytes, st, {{cost, (size_t)b}},
+                      [&](const EmdPlan& p, T* w) {
+                        launch_approxmatch<T>(xyz1, xyz2, b, n, m, match, cost, p, w, st);
+                      });
 }
 
 template <typename T>
 int matchcost(const T* xyz1, const T* xyz2, const T* match, int b, int n, int m, T* cost,
               void* ws, size_t ws_bytes, hipStream_t st) {
-  PCFM_CHECK_ARG(b >= 0 && n >= 0 && m >= 0, "matchcost: negative size");
-  PCFM_CHECK_ARG(ws_bytes >= emd_ws_elems(b, n, m) * sizeof(T),
-                 "matchcost: workspace %zu < %zu bytes", ws_bytes,
-                 emd_ws_elems(b, n, m) * sizeof(T));
-  if (b == 0) return PCFM_OK;
-  if (n == 0 || m == 0) {
-    hipError_t e = hipMemsetAsync(cost, 0, (size_t)b * sizeof(T), st);
-    if (e != hipSuccess) {
-      set_error("matchcost: hipMemsetAsync: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return PCFM_OK;
-  }
-  EmdWs<T> w = carve<T>(ws, b, n, m);
-  const int S = emd_splits(b, n, m);
-  dim3 g(ceil_div(n, kThreads), S, b);
-  hipLaunchKernelGGL(emd_cost_kernel<T>, g, dim3(kThreads), 0, st, xyz1, xyz2, match, b, n, m, S,
-                     w.part);
-  const int per_b = S * (int)g.x;
-  hipLaunchKernelGGL(emd_cost_fin_kernel<T>, dim3(b), dim3(64), 0, st, (const T*)w.part, per_b,
-                     cost);
-  return check_launch("matchcost");
+  return emd_entry<T>("matchcost", b, n, m, ws, ws_bytes, st, {{cost, (size_t)b}},
+                      [&](const EmdPlan& p, T* w) {
+                        const dim3 g(ceil_div(n, kThreads), p.S, b);
+                        hipLaunchKernelGGL(emd_cost_kernel<T>, g, dim3(kThreads), 0, st, xyz1,
+                                           xyz2, match, b, n, m, p.S, w + p.part);
+                        hipLaunchKernelGGL(emd_cost_fin_kernel<T>, dim3(b), dim3(64), 0, st,
+                                           (const T*)(w + p.part), p.S * (int)g.x, cost);
+                      });
 }
 
 template <typename T>
 int matchcost_bwd(const T* gcost, const T* xyz1, const T* xyz2, const T* match, int b, int n,
                   int m, T* grad1, T* grad2, void* ws, size_t ws_bytes, hipStream_t st) {
-  PCFM_CHECK_ARG(b >= 0 && n >= 0 && m >= 0, "matchcost_bwd: negative size");
-  PCFM_CHECK_ARG(ws_bytes >= emd_ws_elems(b, n, m) * sizeof(T),
-                 "matchcost_bwd: workspace %zu < %zu bytes", ws_bytes,
-                 emd_ws_elems(b, n, m) * sizeof(T));
-  if (b == 0) return PCFM_OK;
-  if (n == 0 || m == 0) {
-    hipError_t e = hipSuccess;
-    if (n) e = hipMemsetAsync(grad1, 0, (size_t)b * n * 3 * sizeof(T), st);
-    if (m && e == hipSuccess) e = hipMemsetAsync(grad2, 0, (size_t)b * m * 3 * sizeof(T), st);
-    if (e != hipSuccess) {
-      set_error("matchcost_bwd: hipMemsetAsync: %s", hipGetErrorString(e));
-      return (int)e;
-    }
-    return PCFM_OK;
-  }
-  EmdWs<T> w = carve<T>(ws, b, n, m);
-  const int S = emd_splits(b, n, m);
-  hipLaunchKernelGGL(emd_grad1_kernel<T>, dim3(ceil_div(n, kThreads), S, b), dim3(kThreads), 0,
-                     st, xyz1, xyz2, match, b, n, m, S, w.part);
-  hipLaunchKernelGGL(emd_grad1_fin_kernel<T>, grid1d((size_t)b * n * 3), dim3(256), 0, st,
-                     w.part, S, b, n, gcost, grad1);
-  hipLaunchKernelGGL(emd_grad2_kernel<T>, dim3(m, b), dim3(kThreads), 0, st, xyz1, xyz2, match,
-                     gcost, n, m, grad2);
-  return check_launch("matchcost_bwd");
+  return emd_entry<T>(
+      "matchcost_bwd", b, n, m, ws, ws_bytes, st,
+      {{grad1, (size_t)b * n * 3}, {grad2, (size_t)b * m * 3}}, [&](const EmdPlan& p, T* w) {
+        hipLaunchKernelGGL(emd_grad1_kernel<T>, dim3(ceil_div(n, kThreads), p.S, b),
+                           dim3(kThreads), 0, st, xyz1, xyz2, match, b, n, m, p.S, w + p.part);
+        hipLaunchKernelGGL(emd_grad1_fin_kernel<T>, grid1d(p.bn * 3), dim3(256), 0, st,
+                           (const T*)(w + p.part), p.S, b, n, gcost, grad1);
+        hipLaunchKernelGGL(emd_grad2_kernel<T>, dim3(m, b), dim3(kThreads), 0, st, xyz1, xyz2,
+                           match, gcost, n, m, grad2);
+      });
 }
 
 }  // namespace
@@ -781,7 +637,7 @@ using namespace pcfm;
 
 extern "C" size_t pcfm_emd_workspace_bytes(int b, int n, int m, int elem_bytes) {
   if (b < 0 || n < 0 || m < 0 || (elem_bytes != 4 && elem_bytes != 8)) return 0;
-  return emd_ws_elems(b, n, m) * (size_t)elem_bytes;
+  return EmdPlan(b, n, m, (size_t)elem_bytes).bytes;
 }
 
 extern "C" int pcfm_emd_approxmatch_f32(const float* xyz1, const float* xyz2, int b, int n, int m,

@@ -1,4 +1,4 @@
-"""Subprocess of tests/test_gpu_ops.py::test_emd_rowpass_form_matches_split_form: runs
+"""Subprocess of tests/test_gpu_ops.py::test_emd_fused_pass_matches_unfused: runs
 approxmatch on a fixed set of shapes under the PCFM_EMD_FORM the parent set,
 saves the match matrices to argv[1] (.npz) and
 the mean launch time at B=8, N=M=2048 (the metric's EMD size) to argv[2]."""

@@ -8,12 +8,18 @@ per-element expression), scatter sums to 1e-6 relative (summation order only,
 as the reference's own float atomics).  Everything goes through the reference
 entry-point names on pcfm.ops with CPU tensors.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import oracle as O
 from pcfm import ops
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import emd_ref  # noqa: E402
 
 RNG = np.random.default_rng(20261016)
 
@@ -189,3 +195,29 @@ def test_emd_against_oracle(dtype, b, n, m):
     e1, e2 = O.emd_matchcost_bwd(gc, a, c, e_match)
     _close(g1, e1, rtol=1e-3, atol=1e-4)
     _close(g2, e2, rtol=1e-3, atol=1e-4)
+
+
+# The fp64 reference of approxmatch (tests/helpers/emd_ref.py) against the two CPU
+# implementations.  Each bound is four times the largest deviation measured over
+# emd_ref.CPU_CASES (max |x - ref| / max ref; the deviation is a round-off walk that
+# moves with seed and shape):
+#   cpu_ops f32 4.212e-06, cpu_ops f64 1.708e-06 (its exp is exact, the reference's
+#   is the kernels' float32 exp2), oracle f32 6.973e-06, oracle f64 4.602e-06.
+EMD_REF_BOUND = {("cpu", np.float32): 4 * 4.212e-06, ("cpu", np.float64): 4 * 1.708e-06,
+                 ("oracle", np.float32): 4 * 6.973e-06, ("oracle", np.float64): 4 * 4.602e-06}
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("b,n,m", emd_ref.CPU_CASES)
+def test_emd_fp64_reference_against_cpu_and_oracle(dtype, b, n, m):
+    a, c = emd_ref.clouds(b, n, m, dtype, 1000 * n + m)
+    ref = emd_ref.approxmatch(a, c)
+    assert ref.shape == (b, m, n) and ref.dtype == np.float64 and (ref >= 0).all()
+    # no point gives or takes more than its capacity (emd_kernel.cu:27-33)
+    multi_l, multi_r = (1.0, float(n // m)) if n >= m else (float(m // n), 1.0)
+    assert ref.sum(axis=1).max() <= multi_l + 1e-9 and ref.sum(axis=2).max() <= multi_r + 1e-9
+    got = {"cpu": ops.approxmatch_forward(_t(a), _t(c)).numpy(), "oracle": O.emd_approxmatch(a, c)}
+    for who, x in got.items():
+        err = emd_ref.rel_err(x, ref)
+        print(f"emd_ref {who} {np.dtype(dtype).name} {(b, n, m)}: {err:.3e}")
+        assert err <= EMD_REF_BOUND[who, dtype], (who, err)

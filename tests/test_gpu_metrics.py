@@ -187,8 +187,8 @@ def test_pairwise_emd_matches_one_pair_calls(ops):
     arithmetic does not depend on the batch size -- every pass is grid
     (ceil(rows / 64), b) with the columns split over the block's 16 waves, the
     match/cost kernel grid (ceil(n / 256), ceil(m / 64), b) and the cost finalize
-    one block per element over those partials.  (Only the PCFM_EMD_FORM=split
-    measurement form sizes its column splits by b.)"""
+    one block per element over those partials.  (The split count S that
+    depends on b sizes only matchcost's and its backward's partials.)"""
     from pcfm import metrics
     g = torch.Generator(device=DEV).manual_seed(12)
     n = 100

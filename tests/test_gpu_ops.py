@@ -11,11 +11,17 @@ Bar (DESIGN.md "Parity"):
     to the summand magnitude);
   * EMD (reference built with --use_fast_math, hardware exp): rtol 1e-4.
 """
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
 from oracle import oracle as O
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "helpers"))
+import emd_ref  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -471,41 +477,74 @@ def test_chamfer_c2_product_path(tmp_path, report):
     assert d["bwd_close"], d
 
 
-def test_emd_rowpass_form_matches_split_form(tmp_path, report):
-    """approxmatch's row-pass form (one launch per pass of each level, the
-    finalize in the same block, the 16 column slices of a row summed in a fixed
-    order; a level's third pass and the next level's first share one launch:
-    21 launches; bit-identical to the unfused 31) against the split form (every pass and finalize its own
-    launch, S-way partial sums: 62): the same matches to fp32 round-off over
-    f32/f64, n >< m and ragged sizes (tests/helpers/emd_forms.py;
-    emd_kernel.cu:24-156) -- the two differ only in the order of the column
-    sums -- and the launch time of each at B=8, N=2048."""
+def test_emd_fused_pass_matches_unfused(tmp_path, report):
+    """approxmatch's row passes (one launch per pass of each level, the finalize
+    in the same block, the 16 column slices of a row summed in a fixed order):
+    a level's third pass and the next level's first share one launch (21 pass
+    launches), and the column sums of both are taken in the order of the two
+    separate launches, so the match is bit-identical to PCFM_EMD_FORM=unfused
+    (31) over f32/f64, n >< m and ragged sizes (tests/helpers/emd_forms.py;
+    emd_kernel.cu:24-156); and the launch time of each at B=8, N=2048."""
     import json
     import os
     import subprocess
     import sys
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     res = {}
-    for form in ("split", "rowpass", "unfused"):
+    for form in ("rowpass", "unfused"):
         env = dict(os.environ, PCFM_EMD_FORM=form)
         subprocess.run([sys.executable, os.path.join(repo, "tests", "helpers", "emd_forms.py"),
                         str(tmp_path / f"m{form}.npz"), str(tmp_path / f"t{form}.json")],
                        check=True, timeout=120, env=env, cwd=repo)
         res[form] = json.load(open(tmp_path / f"t{form}.json"))
-    a, b = np.load(tmp_path / "msplit.npz"), np.load(tmp_path / "mrowpass.npz")
-    u = np.load(tmp_path / "munfused.npz")
-    for k in b.files:  # level j's third pass fused with level j+1's first: same sums, same order
+    b, u = np.load(tmp_path / "mrowpass.npz"), np.load(tmp_path / "munfused.npz")
+    assert len(b.files) == 6 and sorted(b.files) == sorted(u.files)
+    for k in b.files:
+        assert np.isfinite(b[k]).all(), k
         np.testing.assert_array_equal(b[k], u[k], err_msg=k)
-    worst = 0.0
-    for k in a.files:
-        x, y = a[k], b[k]
-        assert x.shape == y.shape and np.isfinite(y).all(), k
-        tol = 1e-9 if x.dtype == np.float64 else 2e-5
-        err = float(np.abs(x - y).max()) / max(float(np.abs(x).max()), 1e-30)
-        worst = max(worst, err) if x.dtype != np.float64 else worst
-        assert err <= tol, (k, err)
-        np.testing.assert_allclose(x.sum(axis=(1, 2)), y.sum(axis=(1, 2)), rtol=tol * 10, err_msg=k)
-    report("emd_forms", {"split_ms": res["split"]["approxmatch_ms_b8_n2048"],
-                         "rowpass_ms": res["rowpass"]["approxmatch_ms_b8_n2048"],
-                         "rowpass_unfused_ms": res["unfused"]["approxmatch_ms_b8_n2048"],
-                         "max_rel_diff_f32": worst})
+    report("emd_forms", {"rowpass_ms": res["rowpass"]["approxmatch_ms_b8_n2048"],
+                         "rowpass_unfused_ms": res["unfused"]["approxmatch_ms_b8_n2048"]})
+
+
+# f32: 1e-4; f64: 4 x 4.600e-07 (see test_emd_vs_fp64_reference)
+EMD_REF_BOUND = {"f32": 1e-4, "f64": 4 * 4.600e-07}
+
+
+@pytest.mark.parametrize("b,n,m,dt", [(b, n, m, dt) for b, n, m, dts in emd_ref.GPU_CASES
+                                      for dt in dts])
+def test_emd_vs_fp64_reference(b, n, m, dt):
+    """approxmatch_forward, and the match approxmatch_cost_forward writes, against
+    the numpy fp64 reference of what the kernels define (tests/helpers/emd_ref.py:
+    their d2, their float32 exp2 argument, exp2 rounded to float32; every sum, the
+    divisions and the clamps in fp64), at the smallest shapes that reach each way
+    the kernels can go wrong (emd_ref.GPU_CASES).  Error = max |x - ref| / max ref,
+    and the per-batch totals to ten times the bound.
+
+    The bound is four times the largest deviation of the retired split form
+    (PCFM_EMD_FORM=split at the commit before it was removed) over these cases,
+    per dtype, measured on MI355X (tools/emd_parity.py --ref;
+    profiles/emd_core_parity.json):
+        split form   f32 4.454e-05   f64 4.600e-07
+        default form f32 4.454e-05   f64 4.600e-07
+    For f32 that gives 1.78e-04, above the project's EMD bar of 1e-4
+    (tests/test_gpu_metrics.py), so the bound is the bar itself, 1e-4: the tighter
+    of the two.  The f32 figure comes from one case, (3, 100, 37): every other
+    f32 case is below 8e-06 in both forms.  There 100 points bid for a capacity
+    of 74, some points of xyz1 have suml below 1e-9 at the first levels, their
+    ratioL = remainL / (1e-9 + suml) reaches 1e9, and fp32 round-off in remainR
+    is amplified to 5e-05 in remainL at level 3 -- a property of the iteration
+    in fp32, not of a kernel: pcfm.cpu_ops in fp32 is 6.0e-05 from the reference
+    on the same clouds, and in fp64 3.6e-07."""
+    from pcfm import ops
+    a, c = emd_ref.clouds(b, n, m, np.float32 if dt == "f32" else np.float64, 1000 * n + m)
+    ref = emd_ref.approxmatch(a, c)
+    tol = EMD_REF_BOUND[dt]
+    for name, match in (("approxmatch", ops.approxmatch_forward(cu(a), cu(c))),
+                        ("approxmatch_cost", ops.approxmatch_cost_forward(cu(a), cu(c))[0])):
+        x = np_(match)
+        assert x.shape == ref.shape and np.isfinite(x).all(), name
+        err = emd_ref.rel_err(x, ref)
+        print(f"emd_ref {name} {dt} {(b, n, m)}: {err:.3e}")
+        assert err <= tol, (name, err)
+        np.testing.assert_allclose(x.sum(axis=(1, 2), dtype=np.float64), ref.sum(axis=(1, 2)),
+                                   rtol=10 * tol, err_msg=name)

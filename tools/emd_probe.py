@@ -1,6 +1,7 @@
-"""EMD forward at the bench size (B=8, N=M=2048): wall ms per call (events
-and host clock) for the default form and PCFM_EMD_FORM=split, one JSON line
-each.  Run under rocprofv3 --kernel-trace --stats for the per-kernel split."""
+"""EMD at the bench size (B=8, N=M=2048), default form: ms per call (events and
+host clock) of the forward with match kept, the cost-only forward and forward
+plus backward, one JSON line each.  Run under rocprofv3 --kernel-trace --stats
+for the per-kernel split; PCFM_LIB selects the library (A/B of two builds)."""
 import json
 import os
 import sys
@@ -21,23 +22,36 @@ def main():
     b, n = 8, int(sys.argv[1]) if len(sys.argv) > 1 else 2048
     p1 = torch.rand(b, n, 3, device=dev, generator=g)
     p2 = torch.rand(b, n, 3, device=dev, generator=g)
-    for form in ("rowpass", "split"):
-        os.environ["PCFM_EMD_FORM"] = form
-        x = p1.detach().requires_grad_(True)  # the forward a backward follows: match kept
+    x = p1.detach().requires_grad_(True)  # the forward a backward follows: match kept
+
+    def fwd_match():
+        return earth_mover_distance(x, p2, transpose=False)
+
+    def fwd_cost_only():
+        return earth_mover_distance(p1, p2, transpose=False)
+
+    def fwd_bwd():
+        x.grad = None
+        d = earth_mover_distance(x, p2, transpose=False)
+        d.sum().backward()
+        return d
+
+    for what, fn in (("fwd_match", fwd_match), ("fwd_cost_only", fwd_cost_only),
+                     ("fwd_bwd", fwd_bwd)):
         for _ in range(3):
-            earth_mover_distance(x, p2, transpose=False)
+            fn()
         torch.cuda.synchronize(dev)
         reps = 20
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         e0.record()
         for _ in range(reps):
-            d = earth_mover_distance(x, p2, transpose=False)
+            d = fn()
         e1.record()
         torch.cuda.synchronize(dev)
         host = (time.perf_counter() - t0) * 1e3 / reps
-        print(json.dumps({"form": form, "b": b, "n": n, "fwd_ms_events": e0.elapsed_time(e1) / reps,
-                          "fwd_ms_host": host, "cost0": float(d[0])}), flush=True)
+        print(json.dumps({"what": what, "b": b, "n": n, "ms_events": e0.elapsed_time(e1) / reps,
+                          "ms_host": host, "cost0": float(d.detach()[0])}), flush=True)
 
 
 if __name__ == "__main__":
