@@ -180,6 +180,19 @@ CROSS_SIGNATURES = {
 
 CROSS_ABI_VERSION = 1
 
+# name -> (restype, argtypes); every symbol of include/pcfm_fps.h (farthest-point
+# sampling, the subsample pcfm.metrics takes: a third sibling header with its own
+# version, disjoint from the three tables above)
+FPS_SIGNATURES = {
+    "pcfm_fps_abi_version": (_I, []),
+    "pcfm_fps_supported": (_I, [_I]),
+    "pcfm_fps_resident_points": (_I, []),
+    "pcfm_fps_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "pcfm_fps": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _Z, _P]),
+}
+
+FPS_ABI_VERSION = 1
+
 _lock = threading.Lock()
 _lib = None
 
@@ -201,7 +214,7 @@ def load() -> ctypes.CDLL:
                     "`python -c 'import __graft_entry__ as g; g.build()'` "
                     "(HIP tensors have no fallback)")
             lib = ctypes.CDLL(LIB_PATH)
-            for table in (SIGNATURES, ND_SIGNATURES, CROSS_SIGNATURES):
+            for table in (SIGNATURES, ND_SIGNATURES, CROSS_SIGNATURES, FPS_SIGNATURES):
                 for name, (res, args) in table.items():
                     fn = getattr(lib, name)
                     fn.restype = res
@@ -217,6 +230,10 @@ def load() -> ctypes.CDLL:
             if v != CROSS_ABI_VERSION:
                 raise RuntimeError(f"pcfm: chamfer_cross ABI version {v} != expected "
                                    f"{CROSS_ABI_VERSION}; rebuild")
+            v = lib.pcfm_fps_abi_version()
+            if v != FPS_ABI_VERSION:
+                raise RuntimeError(f"pcfm: fps ABI version {v} != expected "
+                                   f"{FPS_ABI_VERSION}; rebuild")
             _lib = lib
     return _lib
 

@@ -32,6 +32,7 @@ __all__ = [
     "trilinear_devoxelize_backward", "ball_query", "grouping_forward", "grouping_backward",
     "chamfer_forward", "chamfer_backward", "approxmatch_forward", "matchcost_forward",
     "matchcost_backward", "chamfer_nd_forward", "chamfer_nd_backward", "chamfer_cross_forward",
+    "farthest_point_sample",
 ]
 
 # rows of the query set per pairwise block (bounds the (rows, M) temporaries)
@@ -286,6 +287,38 @@ def chamfer_cross_forward(a: torch.Tensor, b: torch.Tensor):
         ab[i] = (_nn(ai, b)[0].double().sum(dim=1) / n).float()
         ba[i] = (_nn(b, ai)[0].double().sum(dim=1) / m).float()
     return ab, ba
+
+
+# ---------------------------------------------------------------------------
+# farthest-point sampling (include/pcfm_fps.h, csrc/fps.hip)
+# ---------------------------------------------------------------------------
+def farthest_point_sample(points: torch.Tensor, m: int, start=None):
+    """points (B, N, D) float32, N >= 1 -> (idx (B, m) int32, out (B, m, D)): the
+    contract of include/pcfm_fps.h.  idx[:, 0] = start clamped to [0, N - 1] (0
+    without one); each later pick is the LOWEST index that maximises the minimum,
+    over the picks so far, of the float32 chain distance (_sqdist / _sqdist_nd of
+    the differences p_i - p_sel) over the first min(D, 3) components."""
+    b, n, d = points.shape
+    k = min(d, 3)
+    pos = points[..., :k]
+    idx = torch.zeros((b, m), dtype=torch.int32)
+    if m == 0 or b == 0:
+        return idx, torch.empty((b, m, d), dtype=points.dtype)
+    rows = torch.arange(b)
+    sel = torch.zeros(b, dtype=torch.long) if start is None else start.long().clamp(0, n - 1)
+    dmin = torch.full((b, n), float("inf"), dtype=points.dtype)
+    idx[:, 0] = sel.to(torch.int32)
+    for j in range(1, m):
+        diff = pos - pos[rows, sel][:, None, :]
+        dist = _sqdist(diff[..., 0], diff[..., 1], diff[..., 2]) if k == 3 else _sqdist_nd(diff)
+        dmin = torch.minimum(dmin, dist)
+        # the lowest index among equal maxima, as _argmin_first of pcfm.metrics
+        top = dmin.max(dim=1, keepdim=True).values
+        sel = torch.where(dmin == top, torch.arange(n)[None, :], n).min(dim=1).values
+        sel = sel.clamp_max(n - 1)      # a row without a maximum (NaN): still an index
+        idx[:, j] = sel.to(torch.int32)
+    out = torch.gather(points, 1, idx.long()[:, :, None].expand(-1, -1, d))
+    return idx, out
 
 
 # ---------------------------------------------------------------------------

@@ -10,6 +10,10 @@ Every one of them reduces an (S, R) matrix of cloud-to-cloud distances:
   * pairwise_emd -- the approximate-match cost of PyTorchEMD over gathered
     chunks of pairs (ops.approxmatch_cost_forward, no match matrix written).
 
+Clouds larger than the matrices can take (or of different sizes) are first cut
+to n_points points each by farthest-point sampling: subsample, one launch of
+csrc/fps.hip per set through ops.farthest_point_sample.
+
 Rows are generated clouds, columns reference clouds.  Nothing here needs a
 gradient: everything runs under torch.no_grad(), and every output is on the
 inputs' device (HIP tensors take the kernels, CPU tensors pcfm.cpu_ops).
@@ -20,7 +24,8 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["pairwise_chamfer", "pairwise_emd", "mmd_cov", "one_nna", "generation_metrics"]
+__all__ = ["pairwise_chamfer", "pairwise_emd", "mmd_cov", "one_nna", "generation_metrics",
+           "subsample"]
 
 # pairs per approxmatch call, at most (the batch is a grid dimension of its kernels)
 _EMD_MAX_PAIRS = 32767
@@ -33,6 +38,21 @@ def pairwise_chamfer(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     which for one pair is pcfm.sample.chamfer_l2."""
     ab, ba = ops.chamfer_cross_forward(x.contiguous(), y.contiguous())
     return ab + ba
+
+
+@torch.no_grad()
+def subsample(clouds: torch.Tensor, m: int, start=None) -> torch.Tensor:
+    """clouds (S, N, D) float32, D in {2, 3, 5, 6} -> (S, m, D): m points of each
+    cloud chosen by farthest-point sampling over the position (the first
+    min(D, 3) components; ops.farthest_point_sample), the rows copied bit for
+    bit.  start (S,) int32: each cloud's first pick (index 0 without one).  The
+    published protocol compares clouds of about 2048 points; m > N raises
+    ValueError."""
+    if clouds.dim() != 3:
+        raise ValueError(f"subsample: expected (S, N, D), got {tuple(clouds.shape)}")
+    if not 0 <= m <= clouds.shape[1]:
+        raise ValueError(f"subsample: m = {m} outside [0, N = {clouds.shape[1]}]")
+    return ops.farthest_point_sample(clouds.contiguous(), m, start)[1]
 
 
 def _emd_chunk_bytes(pairs: int, n: int, m: int, like: torch.Tensor) -> int:
@@ -153,12 +173,18 @@ def one_nna(mxx: torch.Tensor, mxy: torch.Tensor, myy: torch.Tensor) -> dict:
 
 
 @torch.no_grad()
-def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True) -> dict:
+def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True,
+                       n_points=None) -> dict:
     """sample (S, N, D), ref (R, M, D) float32 -> {mmd_cd, mmd_smp_cd, cov_cd,
     1nna_cd, 1nna_gen_cd, 1nna_ref_cd} and, with emd=True, the same six with
     _emd.  Chamfer runs over all D components (D in {2, 3, 5, 6}); EMD over the
     first three (xyz) and needs N == M.  The S x S and R x R matrices of 1-NNA
-    come from the same kernels, a set against itself."""
+    come from the same kernels, a set against itself.  n_points: both sets go
+    through subsample(., n_points) before any matrix is formed, so sets whose
+    clouds differ in size (or are too large for the EMD matrix) compare at
+    n_points points each; None compares the clouds as given."""
+    if n_points is not None:
+        sample, ref = subsample(sample, n_points), subsample(ref, n_points)
     sample, ref = sample.contiguous(), ref.contiguous()
 
     def reduce(pairwise, a, b, tag):

@@ -695,6 +695,44 @@ def chamfer_cross_forward(a: torch.Tensor, b: torch.Tensor):
 
 
 # --------------------------------------------------------------------------
+# farthest-point sampling (include/pcfm_fps.h, csrc/fps.hip): the even subsample
+# pcfm.metrics takes.  The contract is the header's (ties go to the lowest index);
+# the reference-named backend.furthest_point_sampling above still raises.
+# --------------------------------------------------------------------------
+def farthest_point_sample(points: torch.Tensor, m: int, start=None, gather: bool = True):
+    """points (B, N, D) float32, D in {2, 3, 5, 6} -> (idx (B, m) int32, out (B, m, D)
+    float32, or None with gather=False).  idx[:, 0] = start (B,) int32 clamped to
+    [0, N - 1], 0 without one; each later pick is the lowest index farthest, over
+    the first min(D, 3) components, from the picks so far; out = the picked rows,
+    all D components, bit for bit.  m > N is allowed (index 0 repeats)."""
+    host = _host(points, start)
+    (_check_host if host else _check)(points, "points", "f")
+    if points.dim() != 3:
+        raise RuntimeError(f"expected points (B, N, D), got {tuple(points.shape)}")
+    b, n, d = points.shape
+    if d not in (2, 3, 5, 6):
+        raise RuntimeError(f"unsupported point dimension {d}")
+    m = int(m)
+    if m < 0:
+        raise RuntimeError(f"m = {m} is negative")
+    if n == 0 and b > 0 and m > 0:
+        raise RuntimeError("no point to sample from (N = 0)")
+    if start is not None:
+        (_check_host if host else _check)(start, "start", "i")
+        if tuple(start.shape) != (b,):
+            raise RuntimeError(f"start has shape {tuple(start.shape)}, expected {(b,)}")
+    if host:
+        idx, out = cpu_ops.farthest_point_sample(points, m, start)
+        return idx, (out if gather else None)
+    idx = torch.empty((b, m), dtype=torch.int32, device=points.device)
+    out = torch.empty((b, m, d), dtype=torch.float32, device=points.device) if gather else None
+    ws = _workspace(_lib.query("pcfm_fps_workspace_bytes", b, n, m, d), points)
+    _lib.call("pcfm_fps", _ptr(points), b, n, d, m, _ptr(start) if start is not None else None,
+              _ptr(idx), _ptr(out) if gather else None, _ptr(ws), ws.numel(), _stream(points))
+    return idx, out
+
+
+# --------------------------------------------------------------------------
 # emd_cuda (PyTorchEMD/cuda/emd.cpp:8-27): float and double
 # --------------------------------------------------------------------------
 def _emd_check(xyz1, xyz2):
