@@ -19,7 +19,7 @@ namespace {
 // Spatially culled search (large clouds).  Brute force evaluates all N*M
 // pairs at ~9 VALU lane-operations each, i.e. it is VALU-bound; here both
 // clouds are put in Morton order over a common 32^3 grid (the stable segment
-// sort of segsum.hpp), candidates are cut into tiles of 64 consecutive sorted
+// sort of segsum.hip), candidates are cut into tiles of 64 consecutive sorted
 // points with their bounding boxes, and a wave of 64 x kCQ consecutive sorted
 // queries visits the tiles nearest in Morton order first and then every tile
 // whose box can still hold a candidate at a distance <= the wave's worst
@@ -374,13 +374,10 @@ int chamfer_cull(const float* xyz1, const float* xyz2, int b, int n, int m, floa
                      w.key1);
   hipLaunchKernelGGL(cham_key_kernel, dim3(ceil_div(m, 256), b), dim3(256), 0, st, xyz2, m, w.grid,
                      w.key2);
-  int e = allow_big_lds((const void*)seg_sort_kernel);
+  int e = seg_sort(w.key1, (long long)n, b, n, V, 0, w.st1, nullptr, nullptr, w.rank1, st);
   if (e) return e;
-  const int span = seg_sort_span(V);
-  hipLaunchKernelGGL(seg_sort_kernel, dim3(seg_sort_parts(V), b), dim3(1024), seg_sort_lds(V), st,
-                     w.key1, (long long)n, n, V, span, w.st1, nullptr, nullptr, w.rank1);
-  hipLaunchKernelGGL(seg_sort_kernel, dim3(seg_sort_parts(V), b), dim3(1024), seg_sort_lds(V), st,
-                     w.key2, (long long)m, m, V, span, w.st2, nullptr, nullptr, w.rank2);
+  e = seg_sort(w.key2, (long long)m, b, m, V, 0, w.st2, nullptr, nullptr, w.rank2, st);
+  if (e) return e;
   hipLaunchKernelGGL(cham_place_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, st, xyz1, n,
                      w.rank1, w.s1);
   hipLaunchKernelGGL(cham_place_kernel, dim3(ceil_div(m, 256), b), dim3(256), 0, st, xyz2, m,

@@ -144,15 +144,6 @@ __device__ __forceinline__ void zero_acc(f32x16 (&acc)[SI][SJ]) {
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
 }
 
-// A 1-D grid's block id dealt to the 8 XCDs in contiguous runs (T1 remap):
-// hardware sends block i to XCD i % 8; the id returned makes each XCD sweep one
-// contiguous eighth of [0, nwg), so concurrently resident blocks share rows in
-// their XCD's L2 instead of streaming them from the Infinity Cache.
-__device__ __forceinline__ int xcd_deal(int id, int nwg) {
-  const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
-  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
-}
-
 // split N consecutive fp32 (same LDS row) into the hi and lo images.  The
 // (__bf16) casts round to nearest even and lower to gfx950's packed
 // v_cvt_pk_bf16_f32 (one instruction per pair), hi is widened back exactly.

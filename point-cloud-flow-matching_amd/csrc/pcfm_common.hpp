@@ -67,6 +67,15 @@ __device__ __forceinline__ double sqdist3(double dx, double dy, double dz) {
   return __builtin_fma(dz, dz, __builtin_fma(dx, dx, dy * dy));
 }
 
+// A 1-D grid's block id dealt to the 8 XCDs in contiguous runs (T1 remap):
+// hardware sends block i to XCD i % 8; the id returned makes each XCD sweep one
+// contiguous eighth of [0, nwg), so concurrently resident blocks share rows in
+// their XCD's L2 instead of streaming them from the Infinity Cache.
+__device__ __forceinline__ int xcd_deal(int id, int nwg) {
+  const int q = nwg / 8, rr = nwg % 8, xcd = id % 8;
+  return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + id / 8;
+}
+
 // Block index walked in reverse (a second pass over data a first pass just
 // read in forward order finds its most recent rows in the Infinity Cache).
 #ifndef PCFM_REV_APPLY

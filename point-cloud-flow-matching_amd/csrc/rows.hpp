@@ -14,11 +14,10 @@
 // and float atomics into HBM.  Gathers here: one block owns (batch, channel
 // group), its row lives in LDS (<= 128 KiB per block), so every random access
 // is an LDS read while HBM only sees coalesced streams.  Scatters run on the
-// sorted segment engine (segsum.hpp: fixed summation order, no float atomics).
+// sorted segment engine (segsum.hip: fixed summation order, no float atomics).
 #pragma once
 
 #include <algorithm>
-#include <cstdlib>
 
 #include "bn_chan.hpp"
 #include "pcfm_common.hpp"
@@ -32,38 +31,17 @@ namespace pcfm {
 // column so providers with side outputs write them once.
 // ---------------------------------------------------------------------------
 
-// idx [b, ni] (+ optional weights [b, ni]); rows of length `nrows`.
+// idx [b, ni], weight 1; rows of length `nrows`.
 struct ProvIdx1 {
   static constexpr int TAPS = 1;
   const int* idx;
-  const float* w;  // nullptr -> weight 1
   int ni;
   int nrows;
   __device__ __forceinline__ void get(int b, int i, bool, int (&id)[1], float (&wt)[1]) const {
-    const size_t o = (size_t)b * ni + i;
-    const int v = idx[o];
+    const int v = idx[(size_t)b * ni + i];
     const bool ok = (unsigned)v < (unsigned)nrows;
     id[0] = ok ? v : 0;
-    wt[0] = ok ? (w ? w[o] : 1.0f) : 0.0f;
-  }
-};
-
-// inds [b, 8, ni], wgts [b, 8, ni] as saved by the devoxelization forward.
-struct ProvIdx8 {
-  static constexpr int TAPS = 8;
-  const int* inds;
-  const float* wgts;
-  int ni;
-  int nrows;
-  __device__ __forceinline__ void get(int b, int i, bool, int (&id)[8], float (&wt)[8]) const {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const size_t o = ((size_t)b * 8 + k) * ni + i;
-      const int v = inds[o];
-      const bool ok = (unsigned)v < (unsigned)nrows;
-      id[k] = ok ? v : 0;
-      wt[k] = ok ? wgts[o] : 0.0f;
-    }
+    wt[0] = ok ? 1.0f : 0.0f;
   }
 };
 
@@ -113,19 +91,16 @@ struct ProvDevox {
       }
     }
     // A corner whose linear index leaves [0, r^3) (coordinates outside [0, r-1])
-    // contributes nothing: (0, 0), as the oracle and the backward's ProvIdx8
-    // treat the stored pair, so forward and backward agree on every point.
-#ifndef PCFM_DEVOX_CHECK_EACH
-    // every corner is inside the volume when the low cell and the high offsets
+    // contributes nothing: (0, 0), as the oracle and the backward treat the
+    // stored pair, so forward and backward agree on every point.
+    // Every corner is inside the volume when the low cell and the high offsets
     // are (the usual case: coords in [0, r-1]); only then are the 8 checks skipped
     const int xi = (int)xl, yi = (int)yl, zi = (int)zl;
     const bool inside = (unsigned)xi < (unsigned)r && (unsigned)yi < (unsigned)r &&
                         (unsigned)zi < (unsigned)r && (unsigned)(xi + (xh != 0)) < (unsigned)r &&
                         (unsigned)(yi + (yh != 0)) < (unsigned)r &&
                         (unsigned)(zi + zh) < (unsigned)r;
-    if (!inside)
-#endif
-    {
+    if (!inside) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         const bool ok = (unsigned)id[k] < (unsigned)r3;
@@ -278,7 +253,8 @@ __global__ void __launch_bounds__(1024)
 }
 
 // The one-channel form (cpb == 1: the r = 32 rows of 32768 voxels, 128 KiB, one
-// 1024-thread block per CU): IPT items per thread per round, every item's
+// 1024-thread block per CU): IPT items per thread per round (2 is what ships:
+// profiles/r04_ab_gather1_ipt.jsonl), every item's
 // loads (coordinates / indices, the epilogue's add) issued before any of them
 // is used -- the plain loop had one item's load chain in flight per thread
 // (its store may alias the next item's loads as far as the compiler knows),
@@ -440,38 +416,15 @@ struct RowPlan {
 constexpr int kLdsFloatsSmall = 16 * 1024;  // 64 KiB: 2 blocks of 512 threads per CU
 constexpr int kLdsFloatsBig = 32 * 1024;    // 128 KiB: 1 block of 1024 threads per CU
 
-inline long long gather_target_blocks() {
-  static const long long t = [] {
-    const char* e = std::getenv("PCFM_GATHER_BLOCKS");  // dev knob (measurement)
-    // 2 per CU: more channels per block amortise the per-item index work
-    // (measured 0.6-0.8x the time of 4 per CU at r = 16 and 8, equal at r = 32)
-    return e != nullptr ? std::max(1LL, std::atoll(e)) : 512LL;
-  }();
-  return t;
-}
-
-// PCFM_GATHER4=0: the per-channel form for cpb == 4 too (A/B knob)
-inline bool gather4_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("PCFM_GATHER4");
-    return !(e != nullptr && e[0] == '0');
-  }();
-  return on;
-}
-
-// items per thread per round of the one-channel gather (PCFM_GATHER1_IPT: 1 =
-// the generic loop; A/B knob)
-inline int gather1_ipt() {
-  static const int v = [] {
-    const char* e = std::getenv("PCFM_GATHER1_IPT");
-    return e != nullptr ? std::max(1, std::atoi(e)) : 2;
-  }();
-  return v;
-}
+// Blocks a gather's grid aims for: 2 per CU -- more channels per block amortise
+// the per-item index work (measured 0.6-0.8x the time of 4 per CU at r = 16 and
+// 8, equal at r = 32; profiles/r04_ab_gather_blocks.jsonl)
+constexpr long long kGatherTargetBlocks = 2 * kCUs;
+constexpr int kGather1Ipt = 2;  // items per thread per round of the one-channel gather
 
 inline RowPlan plan_gather(int B, int C, int V, int NI) {
   RowPlan p;
-  const long long target = gather_target_blocks();
+  const long long target = kGatherTargetBlocks;
   if ((long long)V <= kLdsFloatsSmall) {
     p.threads = 512;
     p.cpb = std::max(1, std::min(C, kLdsFloatsSmall / std::max(V, 1)));
@@ -515,22 +468,16 @@ inline int launch_gather(const float* rows, float* out, int B, int C, int V, int
   }
   RowPlan p = plan_gather(B, C, V, NI);
   dim3 grid(p.psplit, p.groups, B);
-  if (p.use_lds && p.cpb == 4 && C % 4 == 0 && p.threads == 512 && gather4_enabled()) {
+  if (p.use_lds && p.cpb == 4 && C % 4 == 0 && p.threads == 512) {
     int e = allow_big_lds((const void*)gather_rows4_kernel<Prov>);
     if (e) return e;
     hipLaunchKernelGGL((gather_rows4_kernel<Prov>), grid, dim3(512), p.lds_bytes, st, rows, out, C,
                        V, NI, prov, epi, bn);
-  } else if (p.use_lds && p.cpb == 1 && p.threads == 1024 && gather1_ipt() > 1) {
-    int e = allow_big_lds((const void*)gather_rows1_kernel<Prov, 2>);
+  } else if (p.use_lds && p.cpb == 1 && p.threads == 1024) {
+    int e = allow_big_lds((const void*)gather_rows1_kernel<Prov, kGather1Ipt>);
     if (e) return e;
-    e = allow_big_lds((const void*)gather_rows1_kernel<Prov, 4>);
-    if (e) return e;
-    if (gather1_ipt() >= 4)
-      hipLaunchKernelGGL((gather_rows1_kernel<Prov, 4>), grid, dim3(1024), p.lds_bytes, st, rows,
-                         out, C, V, NI, prov, epi, bn);
-    else
-      hipLaunchKernelGGL((gather_rows1_kernel<Prov, 2>), grid, dim3(1024), p.lds_bytes, st, rows,
-                         out, C, V, NI, prov, epi, bn);
+    hipLaunchKernelGGL((gather_rows1_kernel<Prov, kGather1Ipt>), grid, dim3(1024), p.lds_bytes, st,
+                       rows, out, C, V, NI, prov, epi, bn);
   } else if (p.use_lds) {
     int e = allow_big_lds((const void*)gather_rows_kernel<Prov, true>);
     if (e) return e;

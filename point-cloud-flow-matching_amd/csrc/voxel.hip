@@ -221,8 +221,8 @@ extern "C" int pcfm_avg_voxelize_fwd(const float* feat, const int* coords, int b
                        ind);
   // cnt = histogram of ind; out[c, v] = sum_{i in voxel v} feat[c, i] * (1/cnt[v])
   // (per-term product, vox.cu:68)
-  return seg_scatter<1>(feat, ind, n, true, nullptr, r, b, c, n, s, cnt, out, ws, st,
-                        "avg_voxelize_fwd");
+  return seg_scatter(1, feat, ind, n, true, nullptr, r, b, c, n, s, cnt, out, ws, st,
+                     "avg_voxelize_fwd");
 }
 
 extern "C" int pcfm_avg_voxelize_bwd(const float* grad_y, const int* ind, const int* cnt, int b,
@@ -281,8 +281,8 @@ extern "C" int pcfm_trilinear_devoxelize_bwd(const float* grad_y, const int* ind
   // cell q lands on q + (dx r^2 + dy r + dz).  When a fraction is 0 the
   // reference folds that corner onto the low cell with weight exactly 0
   // (trilinear_devox.cu:64-75), so both placements add the same zeros.
-  return seg_scatter<8>(grad_y, inds, 8LL * n, false, wgts, r, b, c, n, s, nullptr, grad_x, ws,
-                        (hipStream_t)stream, "trilinear_devoxelize_bwd");
+  return seg_scatter(8, grad_y, inds, 8LL * n, false, wgts, r, b, c, n, s, nullptr, grad_x, ws,
+                     (hipStream_t)stream, "trilinear_devoxelize_bwd");
 }
 
 // ---------------------------------------------------------------------------
@@ -373,8 +373,8 @@ extern "C" int pcfm_avg_voxelize_plan(const int* coords, int b, int n, int r, in
   if (n > 0)
     hipLaunchKernelGGL(vox_ind_kernel, dim3(ceil_div(n, 256), b), dim3(256), 0, st, coords, n, r,
                        ind);
-  const int e = seg_plan_build<1>(ind, n, true, nullptr, r, b, n, s, cnt,
-                                  seg_plan_carve(plan, b, n, s, 1), st);
+  const int e = seg_plan_build(1, ind, n, true, nullptr, r, b, n, s, cnt,
+                               seg_plan_carve(plan, b, n, s, 1), st);
   return e ? e : check_launch("avg_voxelize_plan");
 }
 
@@ -387,8 +387,8 @@ extern "C" int pcfm_avg_voxelize_fwd_planned(const float* feat, const void* plan
   PCFM_CHECK_ARG(plan != nullptr && ws_bytes >= seg_apply_bytes(b, c, n, s, 1),
                  "avg_voxelize_fwd_planned: workspace too small");
   if (b == 0) return PCFM_OK;
-  const int e = seg_apply<1>(feat, seg_plan_carve(const_cast<void*>(plan), b, n, s, 1), true, r, b,
-                             c, n, s, out, seg_apply_carve(ws, b, c, n, s, 1), (hipStream_t)stream);
+  const int e = seg_apply(1, feat, seg_plan_carve(const_cast<void*>(plan), b, n, s, 1), true, r, b,
+                          c, n, s, out, seg_apply_carve(ws, b, c, n, s, 1), (hipStream_t)stream);
   return e ? e : check_launch("avg_voxelize_fwd_planned");
 }
 
@@ -401,8 +401,8 @@ extern "C" int pcfm_trilinear_devoxelize_bwd_plan(const int* inds, const float* 
   PCFM_CHECK_ARG(plan != nullptr && plan_bytes >= seg_plan_bytes(b, n, s, 8),
                  "trilinear_devoxelize_bwd_plan: plan buffer too small");
   if (b == 0) return PCFM_OK;
-  const int e = seg_plan_build<8>(inds, 8LL * n, false, wgts, r, b, n, s, nullptr,
-                                  seg_plan_carve(plan, b, n, s, 8), (hipStream_t)stream);
+  const int e = seg_plan_build(8, inds, 8LL * n, false, wgts, r, b, n, s, nullptr,
+                               seg_plan_carve(plan, b, n, s, 8), (hipStream_t)stream);
   return e ? e : check_launch("trilinear_devoxelize_bwd_plan");
 }
 
@@ -415,9 +415,9 @@ extern "C" int pcfm_trilinear_devoxelize_bwd_planned(const float* grad_y, const 
   PCFM_CHECK_ARG(plan != nullptr && ws_bytes >= seg_apply_bytes(b, c, n, s, 8),
                  "trilinear_devoxelize_bwd_planned: workspace too small");
   if (b == 0) return PCFM_OK;
-  const int e = seg_apply<8>(grad_y, seg_plan_carve(const_cast<void*>(plan), b, n, s, 8), false,
-                             r, b, c, n, s, grad_x, seg_apply_carve(ws, b, c, n, s, 8),
-                             (hipStream_t)stream);
+  const int e = seg_apply(8, grad_y, seg_plan_carve(const_cast<void*>(plan), b, n, s, 8), false,
+                          r, b, c, n, s, grad_x, seg_apply_carve(ws, b, c, n, s, 8),
+                          (hipStream_t)stream);
   return e ? e : check_launch("trilinear_devoxelize_bwd_planned");
 }
 

@@ -1,7 +1,7 @@
 """Shapes, seeded inputs and runners of tests/test_gpu_seg_ldsrow.py.
 
 The test imports this module for the process's own path (the LDS-row apply of
-csrc/segsum.hpp where the item row fits) and runs it as a script in a child
+csrc/segsum.hip where the item row fits) and runs it as a script in a child
 process with PCFM_SEG_LDSROW=0 (the switch is read once per process), which
 writes the transposing engine's results of the same cases to an .npz.
 
@@ -14,7 +14,7 @@ import sys
 
 import numpy as np
 
-# csrc/segsum.hpp kLdsRowMaxItems: the longest item row the LDS-row apply takes
+# csrc/segsum.hip kLdsRowMaxItems: the longest item row the LDS-row apply takes
 LDS_ROW_MAX_ITEMS = 40000
 
 # name: (b, c, n, r, layout)
@@ -44,6 +44,15 @@ DEVOX = {
     "outside": (2, 6, 3000, 8, "outside"),        # ~30 % outside [0, r-1], below it too
     "fit_below": (1, 2, LDS_ROW_MAX_ITEMS, 4, "inside"),
     "fit_above": (1, 2, LDS_ROW_MAX_ITEMS + 1, 4, "inside"),
+}
+# name: (b, c, n, m, u, layout): grouping backward, key = neighbour index over
+# V = n rows, m * u items.  "repeat": about half of all slots hold one index (the
+# ball query's "repeat the first hit" fill), so a 16-key tile has more than 256
+# items and that row's segment straddles the tile's pieces.
+GROUP = {
+    "plain": (2, 16, 1000, 64, 16, "uniform"),
+    "repeat": (2, 70, 50, 40, 32, "repeat"),
+    "empty": (1, 3, 16, 0, 8, "uniform"),
 }
 FP64_CASES = ("small", "one_voxel", "one_cell", "empty", "sparse", "outside")
 
@@ -95,6 +104,36 @@ def devox_inputs(name):
     else:
         pts = (g.random((b, 3, n)) * (r + 3) - 1.5).astype(np.float32)
     return gy, pts, r
+
+
+def group_inputs(name):
+    """(grad_y (b, c, m, u) f32, idx (b, m, u) i32, n)."""
+    b, c, n, m, u, layout = GROUP[name]
+    g = np.random.default_rng([3, sum(ord(ch) for ch in name)])
+    gy = g.standard_normal((b, c, m, u)).astype(np.float32)
+    idx = g.integers(0, n, (b, m, u)).astype(np.int32)
+    if layout == "repeat":
+        first = g.integers(0, n, (b, 1, 1)).astype(np.int32)
+        idx = np.where(g.random((b, m, u)) < 0.5, first, idx).astype(np.int32)
+    return gy, idx, n
+
+
+def group_reference(name):
+    """(ref (b, c, n) f64, bound (b, c, n) f64): the float64 np.add.at sum and the
+    first-order bound of an fp32 sum of the same terms in any order,
+    k * 2^-24 * sum |term| with k the row's item count -- from the inputs alone."""
+    gy, idx, n = group_inputs(name)
+    b, c, m, u = gy.shape
+    ref = np.zeros((b, c, n), np.float64)
+    mag = np.zeros((b, c, n), np.float64)
+    k = np.zeros((b, n), np.float64)
+    for i in range(b):
+        flat = idx[i].reshape(-1)
+        terms = gy[i].reshape(c, m * u).astype(np.float64)
+        np.add.at(ref[i], (slice(None), flat), terms)
+        np.add.at(mag[i], (slice(None), flat), np.abs(terms))
+        np.add.at(k[i], flat, 1.0)
+    return ref, k[:, None, :] * 2.0 ** -24 * mag
 
 
 def _cu(a):
@@ -181,6 +220,27 @@ def run_devox(name):
     return {k: v.cpu().numpy() for k, v in res.items()}
 
 
+def run_group(name):
+    """{"gx"}: grouping backward into a NaN-filled output; asserts that a second
+    call returns the same bits."""
+    import torch
+    from pcfm import _lib, ops
+    gy, idx, n = group_inputs(name)
+    b, c, m, u = gy.shape
+    g, ix = _cu(gy), _cu(idx)
+    st = torch.cuda.current_stream().cuda_stream
+    outs = []
+    for _ in range(2):
+        gx = _nan((b, c, n))
+        ws = ops._workspace(_lib.query("pcfm_grouping_bwd_workspace_bytes", b, c, n, m, u), g)
+        _lib.call("pcfm_grouping_bwd", g.data_ptr(), ix.data_ptr(), b, c, n, m, u, gx.data_ptr(),
+                  ws.data_ptr(), ws.numel(), st)
+        outs.append(gx)
+    assert torch.equal(outs[0], outs[1]), f"group {name}: two calls differ"
+    torch.cuda.synchronize()
+    return {"gx": outs[0].cpu().numpy()}
+
+
 def devox_grid(name):
     b, c, _, r, _ = DEVOX[name]
     g = np.random.default_rng(_seed("devox", name) + [7])
@@ -195,6 +255,9 @@ def run_all():
     for name in DEVOX:
         for k, v in run_devox(name).items():
             res[f"devox.{name}.{k}"] = v
+    for name in GROUP:
+        for k, v in run_group(name).items():
+            res[f"group.{name}.{k}"] = v
     return res
 
 

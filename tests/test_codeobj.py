@@ -57,6 +57,24 @@ def test_weight_gradient_claims_its_cus(tmp_path):
     assert found == 1
 
 
+@needs_tools
+@pytest.mark.skipif(not os.path.exists(LIB), reason="libpcfm_hip.so not built")
+def test_each_segment_kernel_ships_once(tmp_path):
+    """The segment scatter engine is one translation unit (csrc/segsum.hip): the
+    library carries each of its nine kernels exactly once, and the one-channel
+    gather only with the 2 items per thread that are launched."""
+    names = [k for co in codeobj.extract(LIB, str(tmp_path)) for k in codeobj.kernel_resources(co)]
+    want = ("15seg_sort_kernelE", "16seg_units_kernelILi1EE", "16seg_units_kernelILi8EE",
+            "15seg_rows_kernelE", "20seg_plan_rows_kernelE", "22seg_unit_gather_kernelILi1EE",
+            "22seg_unit_gather_kernelILi8EE", "19seg_part_sum_kernelE", "18seg_ldsrow1_kernelE")
+    counts = {w: sum(w in n for n in names) for w in want}
+    assert all(v == 1 for v in counts.values()), counts
+    assert sum(bool(re.search(r"\d+seg_\w+_kernel", n)) for n in names) == len(want)
+    gather1 = [n for n in names if "gather_rows1_kernel" in n]
+    assert gather1, "no one-channel gather kernel found"
+    assert all(re.search(r"gather_rows1_kernelINS_\w+ELi2EEE", n) for n in gather1), gather1
+
+
 def _librccl():
     import torch
     p = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")

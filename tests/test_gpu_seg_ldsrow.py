@@ -1,4 +1,4 @@
-"""GPU: the scatters whose item row fits LDS (csrc/segsum.hpp, the LDS-row apply:
+"""GPU: the scatters whose item row fits LDS (csrc/segsum.hip, the LDS-row apply:
 one block per (batch, channel) stages in[b, c, :] in sorted order in LDS and
 sums every voxel's segment from there) -- avg_voxelize_fwd and
 trilinear_devoxelize_bwd, planned and unplanned.
@@ -13,7 +13,10 @@ trilinear_devoxelize_bwd, planned and unplanned.
     switch is read once) on every shape -- the voxelization to the bit: the
     LDS-row apply adds in that engine's order -- one of them the longest row
     that fits and one a single item longer;
-  * the devoxelization backward is the forward's adjoint.
+  * the devoxelization backward is the forward's adjoint;
+  * grouping backward (key = neighbour index, V = n rows) on both engines: equal
+    bits, and every element within the first-order bound of an fp32 sum of its
+    terms in any order around a float64 np.add.at.
 
 The runners compute every case once per process; the tests share the results.
 """
@@ -115,6 +118,23 @@ def test_trilinear_devoxelize_bwd(new, name):
     lhs = float((new[f"devox.{name}.fwd"].astype(np.float64) * gy).sum())
     rhs = float((grid.astype(np.float64) * new[f"devox.{name}.gx"]).sum())
     assert abs(lhs - rhs) <= 1e-5 * max(1.0, abs(lhs)), (lhs, rhs)
+
+
+@pytest.mark.parametrize("name", list(cases.GROUP))
+def test_grouping_bwd(new, old, name):
+    """Both engines return the same bits (two calls of each too: asserted by the
+    runner), every element written, each within k * 2^-24 * sum |term| of the
+    float64 sum (k the row's item count; helpers/seg_ldsrow_cases.py)."""
+    ref, bound = cases.group_reference(name)
+    for tag, got in (("lds-row", new[f"group.{name}.gx"]),
+                     ("transposing", old[f"group.{name}.gx"])):
+        assert got.shape == ref.shape, tag
+        assert not np.isnan(got).any(), f"{tag}: an output element was not written"
+        err = np.abs(got.astype(np.float64) - ref)
+        print(f"group {name} {tag}: max err / bound = "
+              f"{float((err / np.maximum(bound, 1e-300)).max()) if err.size else 0.0:.3g}")
+        assert (err <= bound).all(), (tag, float((err - bound).max()))
+    np.testing.assert_array_equal(new[f"group.{name}.gx"], old[f"group.{name}.gx"])
 
 
 def test_new_path_matches_transposing_engine(new, old):
