@@ -193,6 +193,18 @@ FPS_SIGNATURES = {
 
 FPS_ABI_VERSION = 1
 
+# name -> (restype, argtypes); every symbol of include/pcfm_occupancy.h (the
+# occupancy counts behind the metrics' Jensen-Shannon divergence: a fourth sibling
+# header with its own version, disjoint from the four tables above)
+OCCUPANCY_SIGNATURES = {
+    "pcfm_occupancy_abi_version": (_I, []),
+    "pcfm_occupancy_supported": (_I, [_I, _I]),
+    "pcfm_occupancy_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "pcfm_occupancy_counts": (_I, [_P, _I, _I, _I, _I, _P, _P, _Z, _P]),
+}
+
+OCCUPANCY_ABI_VERSION = 1
+
 _lock = threading.Lock()
 _lib = None
 
@@ -214,7 +226,8 @@ def load() -> ctypes.CDLL:
                     "`python -c 'import __graft_entry__ as g; g.build()'` "
                     "(HIP tensors have no fallback)")
             lib = ctypes.CDLL(LIB_PATH)
-            for table in (SIGNATURES, ND_SIGNATURES, CROSS_SIGNATURES, FPS_SIGNATURES):
+            for table in (SIGNATURES, ND_SIGNATURES, CROSS_SIGNATURES, FPS_SIGNATURES,
+                          OCCUPANCY_SIGNATURES):
                 for name, (res, args) in table.items():
                     fn = getattr(lib, name)
                     fn.restype = res
@@ -234,6 +247,10 @@ def load() -> ctypes.CDLL:
             if v != FPS_ABI_VERSION:
                 raise RuntimeError(f"pcfm: fps ABI version {v} != expected "
                                    f"{FPS_ABI_VERSION}; rebuild")
+            v = lib.pcfm_occupancy_abi_version()
+            if v != OCCUPANCY_ABI_VERSION:
+                raise RuntimeError(f"pcfm: occupancy ABI version {v} != expected "
+                                   f"{OCCUPANCY_ABI_VERSION}; rebuild")
             _lib = lib
     return _lib
 

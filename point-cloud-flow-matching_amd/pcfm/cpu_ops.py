@@ -32,7 +32,7 @@ __all__ = [
     "trilinear_devoxelize_backward", "ball_query", "grouping_forward", "grouping_backward",
     "chamfer_forward", "chamfer_backward", "approxmatch_forward", "matchcost_forward",
     "matchcost_backward", "chamfer_nd_forward", "chamfer_nd_backward", "chamfer_cross_forward",
-    "farthest_point_sample",
+    "farthest_point_sample", "occupancy_nodes", "occupancy_counts",
 ]
 
 # rows of the query set per pairwise block (bounds the (rows, M) temporaries)
@@ -319,6 +319,85 @@ def farthest_point_sample(points: torch.Tensor, m: int, start=None):
         idx[:, j] = sel.to(torch.int32)
     out = torch.gather(points, 1, idx.long()[:, :, None].expand(-1, -1, d))
     return idx, out
+
+
+# ---------------------------------------------------------------------------
+# occupancy counts (include/pcfm_occupancy.h, csrc/occupancy.hip)
+# ---------------------------------------------------------------------------
+def _occupancy_kept(r: int) -> torch.Tensor:
+    """(r, r, r) bool: node (i, j, k) is kept iff a^2 + b^2 + c^2 <= (r-1)^2 with
+    a = 2i - (r-1), b and c likewise (integers)."""
+    sq = (2 * torch.arange(r) - (r - 1)) ** 2
+    return sq[:, None, None] + sq[None, :, None] + sq[None, None, :] <= (r - 1) ** 2
+
+
+def _occupancy_rint(u: torch.Tensor, r: int) -> torch.Tensor:
+    """clamp(rint(u), 0, r-1) as int64, half to even; a NaN gives 0."""
+    return torch.nan_to_num(torch.round(u), nan=0.0).clamp(0, r - 1).long()
+
+
+def _occupancy_nearest_kept(u: torch.Tensor, r: int, kept: torch.Tensor) -> torch.Tensor:
+    """u (P, 3) float32 grid coordinates -> (P,) int64: the kept node of LOWEST
+    flat index that minimises _sqdist(u - node) (branch 2 of the header).
+
+    The kernel walks every kept node.  Here the kept k of a column (i, j) are one
+    interval [klo, khi], and fma(dz, dz, dxy) does not decrease with |dz| (each
+    rounding is monotone), so the column's minimum is at the k of the interval
+    nearest to u.z: an (r, r) table of column minima per point, the first column
+    that holds the overall minimum, then the first k of that column's interval
+    that attains it -- the same node as the walk, ties included."""
+    p = u.shape[0]
+    grid = torch.arange(r, dtype=torch.float32)
+    pos, cols = torch.arange(r), torch.arange(r * r)
+    count = kept.sum(dim=2).view(-1)              # kept k per column, symmetric about the centre
+    has = count > 0
+    klo = torch.div(r - count, 2, rounding_mode="floor")
+    khi = r - 1 - klo
+    mid = r // 2
+    out = torch.empty(p, dtype=torch.long)
+    for p0 in range(0, p, 8192):
+        v = u[p0:p0 + 8192]
+        q = v.shape[0]
+        dx, dy, dz = (v[:, a, None] - grid for a in range(3))          # (q, r) float32
+        dxy = _fma32(dx[:, :, None], dx[:, :, None], (dy * dy)[:, None, :]).view(q, -1)
+        near = torch.minimum(torch.maximum(_occupancy_rint(v[:, 2], r)[:, None], klo), khi)
+        dzn = dz.gather(1, near)
+        best = torch.where(has, _fma32(dzn, dzn, dxy), float("inf"))   # column minima
+        low = best.min(dim=1, keepdim=True).values
+        col = torch.where((best == low) & has, cols, r * r).min(dim=1).values
+        col = torch.where(col == r * r, mid * r + mid, col)            # NaN: the centre
+        row = _fma32(dz, dz, dxy.gather(1, col[:, None]))              # (q, r): that column
+        ok = (pos >= klo[col][:, None]) & (pos <= khi[col][:, None]) & (row == low)
+        k = torch.where(ok, pos, r).min(dim=1).values
+        k = torch.where(k == r, mid, k)
+        out[p0:p0 + q] = col * r + k
+    return out
+
+
+def occupancy_nodes(points: torch.Tensor, resolution: int) -> torch.Tensor:
+    """points (S, N, D) float32, D >= 3 -> (S, N) int64: the flat index of the kept
+    node each point counts in (include/pcfm_occupancy.h).  u = fma(p, r-1, (r-1)/2)
+    as the float64 product and sum rounded to float32; branch 1 where rint(u) is
+    kept, the nearest-kept-node search only for the other points."""
+    r = int(resolution)
+    s, n = points.shape[:2]
+    pos = points[..., :3].reshape(-1, 3)
+    u = _fma32(pos, torch.tensor(float(r - 1)), torch.tensor(0.5 * (r - 1)))
+    c = _occupancy_rint(u, r)
+    node = (c[:, 0] * r + c[:, 1]) * r + c[:, 2]
+    kept = _occupancy_kept(r)
+    need = ~kept.view(-1)[node]
+    if need.any():
+        node[need] = _occupancy_nearest_kept(u[need], r, kept)
+    return node.view(s, n)
+
+
+def occupancy_counts(points: torch.Tensor, resolution: int) -> torch.Tensor:
+    """points (S, N, D) float32 -> (r^3,) int32: counts[f] = the points of all S
+    clouds counted in node f (occupancy_nodes); a node that is not kept holds 0."""
+    r = int(resolution)
+    nodes = occupancy_nodes(points, r).reshape(-1)
+    return torch.bincount(nodes, minlength=r ** 3).to(torch.int32)
 
 
 # ---------------------------------------------------------------------------

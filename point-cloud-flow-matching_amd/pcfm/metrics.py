@@ -1,8 +1,9 @@
 """Generation metrics between a set of generated clouds and a set of reference
 clouds: minimum matching distance (MMD), coverage (COV) and 1-nearest-neighbour
-accuracy (1-NNA), under Chamfer distance and under the approximate EMD.
+accuracy (1-NNA), under Chamfer distance and under the approximate EMD, and the
+Jensen-Shannon divergence (JSD) between the two sets' occupancy histograms.
 
-Every one of them reduces an (S, R) matrix of cloud-to-cloud distances:
+Each of the first three reduces an (S, R) matrix of cloud-to-cloud distances:
 
   * pairwise_chamfer -- one launch of the set-against-set kernel
     (csrc/chamfer_cross.hip through ops.chamfer_cross_forward): no cloud is
@@ -13,6 +14,12 @@ Every one of them reduces an (S, R) matrix of cloud-to-cloud distances:
 Clouds larger than the matrices can take (or of different sizes) are first cut
 to n_points points each by farthest-point sampling: subsample, one launch of
 csrc/fps.hip per set through ops.farthest_point_sample.
+
+JSD looks at a set as one distribution of points in space: occupancy_counts, one
+call of csrc/occupancy.hip per set through ops.occupancy_counts, counts the
+points of all clouds of a set on an r x r x r grid (the nodes inside the inscribed
+sphere), and jsd_from_counts takes the divergence of the two normalised
+histograms.
 
 Rows are generated clouds, columns reference clouds.  Nothing here needs a
 gradient: everything runs under torch.no_grad(), and every output is on the
@@ -25,7 +32,7 @@ import torch
 from . import _lib, ops
 
 __all__ = ["pairwise_chamfer", "pairwise_emd", "mmd_cov", "one_nna", "generation_metrics",
-           "subsample"]
+           "subsample", "occupancy_counts", "jsd_from_counts", "jsd"]
 
 # pairs per approxmatch call, at most (the batch is a grid dimension of its kernels)
 _EMD_MAX_PAIRS = 32767
@@ -173,8 +180,81 @@ def one_nna(mxx: torch.Tensor, mxy: torch.Tensor, myy: torch.Tensor) -> dict:
 
 
 @torch.no_grad()
+def occupancy_counts(clouds: torch.Tensor, resolution: int = 28) -> torch.Tensor:
+    """clouds (S, N, D) float32, D in {3, 5, 6}; 3 <= resolution <= 32 -> (r^3,)
+    int32 on the clouds' device: how many points of the whole set count in each
+    node of the r x r x r grid over the cube [-0.5, 0.5]^3 (ops.occupancy_counts;
+    include/pcfm_occupancy.h states the rule).  Only the nodes inside the inscribed
+    sphere take points: a point outside it counts in the nearest node inside.  The
+    clouds are counted as given -- bringing them into the unit cube is the
+    caller's data convention.  r = 28 is the published protocol's resolution.  A
+    bad shape, D = 2 or a resolution outside [3, 32] raises ValueError."""
+    if clouds.dim() != 3:
+        raise ValueError(f"occupancy_counts: expected (S, N, D), got {tuple(clouds.shape)}")
+    if clouds.shape[2] not in (3, 5, 6):
+        raise ValueError(f"occupancy_counts: D = {clouds.shape[2]} is not 3, 5 or 6 (the grid is "
+                         "three-dimensional)")
+    if not 3 <= int(resolution) <= 32:
+        raise ValueError(f"occupancy_counts: resolution = {resolution} outside [3, 32]")
+    return ops.occupancy_counts(clouds.contiguous(), int(resolution))
+
+
+def _kl_bits_sum(w: torch.Tensor, a: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """sum over the entries with w > 0 of w * log2(2 a / t), float64, in index order."""
+    on = w > 0
+    return (w[on] * torch.log2(2.0 * a[on] / t[on])).sum()
+
+
+@torch.no_grad()
+def jsd_from_counts(p_counts: torch.Tensor, q_counts: torch.Tensor) -> torch.Tensor:
+    """Two count vectors of one length -> the Jensen-Shannon divergence of the
+    normalised histograms P = p / sum p, Q = q / sum q, as a 0-dim float64 tensor
+    on the inputs' device: H(M) - (H(P) + H(Q)) / 2 with M = (P + Q) / 2 and H the
+    entropy in bits (0 log 0 = 0), so the value lies in [0, 1].  The sets may
+    differ in size; the normalisation absorbs it.
+
+    It is summed in the equivalent form (KL(P || M) + KL(Q || M)) / 2 over the
+    counts themselves: with a = p * sum q and b = q * sum p,
+        (sum_i p_i log2(2 a_i / (a_i + b_i))) / sum p, the same with q and b, halved.
+    Histograms that are multiples of one another have a == b entry by entry, every
+    logarithm is log2(1) and the result is exactly 0; disjoint supports make every
+    logarithm log2(2), the sums are sums of integers and the result is exactly 1
+    -- which differences of three rounded entropies would not give.
+
+    The two vectors (2 * r^3 * 4 bytes) are copied to the host and the arithmetic
+    runs there in float64, in one fixed order; the result goes back to the
+    inputs' device.  HIP and CPU inputs therefore give the same bits, at the cost
+    of one small copy and a synchronisation per call.  An empty histogram (sum 0)
+    raises ValueError."""
+    if p_counts.dim() != 1 or p_counts.shape != q_counts.shape:
+        raise ValueError(f"jsd_from_counts: expected two vectors of one length, got "
+                         f"{tuple(p_counts.shape)} and {tuple(q_counts.shape)}")
+    if p_counts.device != q_counts.device:
+        raise ValueError("jsd_from_counts: the two vectors are on different devices")
+    p, q = p_counts.detach().cpu().double(), q_counts.detach().cpu().double()
+    if bool((p < 0).any()) or bool((q < 0).any()):
+        raise ValueError("jsd_from_counts: a negative count")
+    sp, sq = p.sum(), q.sum()
+    if float(sp) <= 0 or float(sq) <= 0:
+        raise ValueError("jsd_from_counts: an empty histogram")
+    a, b = p * sq, q * sp
+    t = a + b
+    out = (_kl_bits_sum(p, a, t) / sp + _kl_bits_sum(q, b, t) / sq) / 2
+    return out.clamp(0.0, 1.0).to(p_counts.device)
+
+
+@torch.no_grad()
+def jsd(sample: torch.Tensor, ref: torch.Tensor, resolution: int = 28) -> torch.Tensor:
+    """sample (S, N, D), ref (R, M, D) float32, D in {3, 5, 6} -> the Jensen-Shannon
+    divergence (0-dim float64) between the occupancy histograms of the two sets:
+    jsd_from_counts of their occupancy_counts at `resolution`."""
+    return jsd_from_counts(occupancy_counts(sample, resolution),
+                           occupancy_counts(ref, resolution))
+
+
+@torch.no_grad()
 def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True,
-                       n_points=None) -> dict:
+                       n_points=None, jsd: bool = False, jsd_resolution: int = 28) -> dict:
     """sample (S, N, D), ref (R, M, D) float32 -> {mmd_cd, mmd_smp_cd, cov_cd,
     1nna_cd, 1nna_gen_cd, 1nna_ref_cd} and, with emd=True, the same six with
     _emd.  Chamfer runs over all D components (D in {2, 3, 5, 6}); EMD over the
@@ -182,7 +262,16 @@ def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True
     come from the same kernels, a set against itself.  n_points: both sets go
     through subsample(., n_points) before any matrix is formed, so sets whose
     clouds differ in size (or are too large for the EMD matrix) compare at
-    n_points points each; None compares the clouds as given."""
+    n_points points each; None compares the clouds as given.
+
+    jsd=True adds one key, "jsd": the Jensen-Shannon divergence (0-dim float64)
+    of the two sets' occupancy histograms at jsd_resolution, taken on the clouds
+    AS GIVEN, before the n_points subsample.  Farthest-point sampling evens out
+    density on purpose: a histogram of such a subsample measures the support of
+    a shape, not where its points lie.  N and M may differ (the histograms are
+    normalised); D = 2 raises ValueError.  With jsd=False the result is what it
+    was without the keyword."""
+    extra = {"jsd": _jsd(sample, ref, jsd_resolution)} if jsd else {}
     if n_points is not None:
         sample, ref = subsample(sample, n_points), subsample(ref, n_points)
     sample, ref = sample.contiguous(), ref.contiguous()
@@ -201,4 +290,8 @@ def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True
             raise ValueError("generation_metrics: EMD needs at least three components (xyz)")
         out.update(reduce(pairwise_emd, sample[..., :3].contiguous(), ref[..., :3].contiguous(),
                           "emd"))
+    out.update(extra)
     return out
+
+
+_jsd = jsd      # generation_metrics' keyword shadows the function

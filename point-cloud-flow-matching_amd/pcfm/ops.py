@@ -733,6 +733,41 @@ def farthest_point_sample(points: torch.Tensor, m: int, start=None, gather: bool
 
 
 # --------------------------------------------------------------------------
+# occupancy counts (include/pcfm_occupancy.h, csrc/occupancy.hip): the histogram
+# pcfm.metrics reduces to the Jensen-Shannon divergence.  No reference module has
+# this name; the contract is the header's.
+# --------------------------------------------------------------------------
+def occupancy_counts(points: torch.Tensor, resolution: int = 28) -> torch.Tensor:
+    """points (S, N, D) float32, D in {3, 5, 6}; 3 <= resolution <= 32 -> (r^3,)
+    int32 on the input's device: counts[(i * r + j) * r + k] = the points of all S
+    clouds counted in node (i, j, k) of the r x r x r grid over [-0.5, 0.5]^3.
+    Only the position (the first three components) takes part, the clouds are
+    counted as given; a node outside the inscribed sphere holds 0 and the sum is
+    S * N.  A point counts in the node its grid coordinates round to if that node
+    lies inside the sphere, otherwise in the nearest node that does (the lowest
+    flat index among equals)."""
+    host = _host(points)
+    (_check_host if host else _check)(points, "points", "f")
+    if points.dim() != 3:
+        raise RuntimeError(f"expected points (S, N, D), got {tuple(points.shape)}")
+    s, n, d = points.shape
+    if d not in (3, 5, 6):
+        raise RuntimeError(f"unsupported point dimension {d}")
+    r = int(resolution)
+    if not 3 <= r <= 32:
+        raise RuntimeError(f"resolution = {r} outside [3, 32]")
+    if s * n >= 1 << 31:
+        raise RuntimeError(f"S * N = {s * n} does not fit 31 bits")
+    if host:
+        return cpu_ops.occupancy_counts(points, r)
+    counts = torch.empty((r ** 3,), dtype=torch.int32, device=points.device)
+    ws = _workspace(_lib.query("pcfm_occupancy_workspace_bytes", s, n, d, r), points)
+    _lib.call("pcfm_occupancy_counts", _ptr(points), s, n, d, r, _ptr(counts), _ptr(ws),
+              ws.numel(), _stream(points))
+    return counts
+
+
+# --------------------------------------------------------------------------
 # emd_cuda (PyTorchEMD/cuda/emd.cpp:8-27): float and double
 # --------------------------------------------------------------------------
 def _emd_check(xyz1, xyz2):
