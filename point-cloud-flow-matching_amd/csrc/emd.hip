@@ -33,98 +33,24 @@
 // at 1024 blocks, against ~1.7 us for a kernel boundary); the row passes as 30
 // separate launches with scalar-loaded columns 0.51 ms, with LDS-staged columns
 // and the fused cost 0.39 ms.
-#include "pcfm_common.hpp"
-
-#include <algorithm>
-#include <cstdlib>
-#include <initializer_list>
-#include <utility>
+//
+// The level table, emd_exp2, the finalize expressions, row_at, block_sum, the
+// host plan, the prologue and the launch sequence are emd_core.hpp's, shared
+// with the D-component kernels of emd_nd.hip.
+#include "emd_core.hpp"
 
 namespace pcfm {
 namespace {
 
-constexpr int kLevels = 10;
-// level_j = -4^j for j = 7 .. -1, then 0 (emd_kernel.cu:44-48).
-constexpr float h_levels[kLevels] = {-16384.0f, -4096.0f, -1024.0f, -256.0f, -64.0f,
-                                     -16.0f,    -4.0f,    -1.0f,    -0.25f,  0.0f};
-// level_j * log2(e) in one float factor.  level_j is a power of two, so
-// d2 * (level_j * log2 e) rounds exactly as (level_j * d2) * log2 e.
-constexpr float level_log2e(int j) { return h_levels[j] * 1.4426950408889634f; }
-
-// exp(level * d2) as the hardware exp2 of float(d2) * lvl2, lvl2 = level * log2(e)
-template <typename T>
-__device__ __forceinline__ T emd_exp2(T d2, T lvl2) {
-  return (T)__builtin_amdgcn_exp2f((float)d2 * (float)lvl2);
-}
-
-template <typename T>
-__device__ __forceinline__ T fmaT(T a, T b, T c);
-template <>
-__device__ __forceinline__ float fmaT<float>(float a, float b, float c) {
-  return __builtin_fmaf(a, b, c);
-}
-template <>
-__device__ __forceinline__ double fmaT<double>(double a, double b, double c) {
-  return __builtin_fma(a, b, c);
-}
-
-constexpr int kThreads = 256;
-
-// Row i of batch element bb, clamped to the element's last row: a lane past
-// the end loads a valid row unconditionally and its result is never stored.
-__device__ __forceinline__ size_t row_at(int bb, int nr, int i) {
-  const int ii = i < nr ? i : nr - 1;
-  return (size_t)bb * nr + ii;
-}
-
-// The finalize expressions of a level; fminf / fmaxf take float arguments in
-// the reference for both dtypes.
-// ratioL = remainL / (1e-9 + suml)    (:57, :81)
-template <typename T>
-__device__ __forceinline__ T emd_ratio_l(T remL, T suml) {
-  return remL / ((T)1e-9f + suml);
-}
-// consumption = min(remainR / (sumr + 1e-9), 1); ratioR = consumption * remainR   (:111-115)
-template <typename T>
-__device__ __forceinline__ T emd_ratio_r(T remR, T sumr) {
-  return (T)fminf((float)(remR / (sumr + (T)1e-9f)), 1.0f) * remR;
-}
-// remain = max(0, remain - sum): remainR (:116) and remainL (:150)
-template <typename T>
-__device__ __forceinline__ T emd_remain(T rem, T sum) {
-  return (T)fmaxf(0.0f, (float)(rem - sum));
-}
-
-template <typename T>
-__device__ __forceinline__ T sum_parts(const T* part, int S, size_t stride, size_t i) {
-  T v = 0;
-  for (int s = 0; s < S; ++s) v += part[(size_t)s * stride + i];
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T block_sum(T v, T* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  T t = 0;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
-  return t;  // valid in thread 0
-}
-
 // cost partials: grid = (k blocks, S, b); part[(bb*S + s)*kblocks + kb].
 template <typename T>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kEmdThreads)
     emd_cost_kernel(const T* __restrict__ xyz1, const T* __restrict__ xyz2,
                     const T* __restrict__ match, int b, int n, int m, int S,
                     T* __restrict__ part) {
-  __shared__ T red[kThreads / 64];
+  __shared__ T red[kEmdThreads / 64];
   const int bb = blockIdx.z, s = blockIdx.y;
-  const int k = blockIdx.x * kThreads + threadIdx.x;
+  const int k = blockIdx.x * kEmdThreads + threadIdx.x;
   const T* p1 = xyz1 + row_at(bb, n, k) * 3;
   const T x1 = p1[0], y1 = p1[1], z1 = p1[2];
   const int l0 = (int)(((long long)m * s) / S), l1 = (int)(((long long)m * (s + 1)) / S);
@@ -140,18 +66,11 @@ __global__ void __launch_bounds__(kThreads)
   if (threadIdx.x == 0) part[((size_t)bb * S + s) * gridDim.x + blockIdx.x] = t;
 }
 
-// cost[bb] = sum of the batch element's per_b block partials: one wave per
-// batch element, lanes over strided partials, then a fixed xor tree
-// (deterministic; the serial form was 9 us at 512 partials).
+// cost[bb] = sum of the batch element's per_b block partials (emd_cost_fin).
 template <typename T>
 __global__ void __launch_bounds__(64)
     emd_cost_fin_kernel(const T* __restrict__ part, int per_b, T* __restrict__ cost) {
-  const int bb = blockIdx.x, lane = threadIdx.x;
-  T t = 0;
-  for (int i = lane; i < per_b; i += 64) t += part[(size_t)bb * per_b + i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  if (lane == 0) cost[bb] = t;
+  emd_cost_fin<T>(part, per_b, cost);
 }
 
 // The match write with matchcost fused (the fused forward, pcfm_emd_approxmatch_cost_*):
@@ -162,19 +81,18 @@ __global__ void __launch_bounds__(64)
 // the 4-byte-per-entry match matrix is not read back for the cost.  A block
 // = 256 k (lanes, coalesced rows) x kMatchL l, the l points and their 10
 // ratioR values staged in LDS.
-constexpr int kMatchL = 32;
 template <typename T>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kEmdThreads)
     emd_match_cost_kernel(const T* __restrict__ xyz1, const T* __restrict__ xyz2, int b, int n,
                           int m, const T* __restrict__ levL, const T* __restrict__ levR,
                           T* __restrict__ match, T* __restrict__ part) {
   constexpr int kW = kLevels + 3;  // per l: ratioR_0..9, x, y, z
   __shared__ T sl[kMatchL * kW];
-  __shared__ T red[kThreads / 64];
+  __shared__ T red[kEmdThreads / 64];
   const int bb = blockIdx.z, kb = blockIdx.x, lb = blockIdx.y;
-  const int k = kb * kThreads + threadIdx.x;
+  const int k = kb * kEmdThreads + threadIdx.x;
   const int l0 = lb * kMatchL, nl = min(kMatchL, m - l0);
-  for (int e = threadIdx.x; e < nl * kW; e += kThreads) {
+  for (int e = threadIdx.x; e < nl * kW; e += kEmdThreads) {
     const int li = e / kW, q = e - li * kW;
     sl[e] = q < kLevels ? levR[(size_t)q * b * m + (size_t)bb * m + l0 + li]
                         : xyz2[((size_t)bb * m + l0 + li) * 3 + (q - kLevels)];
@@ -205,12 +123,12 @@ __global__ void __launch_bounds__(kThreads)
 
 // grad1 partials: lanes over k, l split S ways: part[s][(bb*n + k)*3 + x].
 template <typename T>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kEmdThreads)
     emd_grad1_kernel(const T* __restrict__ xyz1, const T* __restrict__ xyz2,
                      const T* __restrict__ match, int b, int n, int m, int S,
                      T* __restrict__ part) {
   const int bb = blockIdx.z, s = blockIdx.y;
-  const int k = blockIdx.x * kThreads + threadIdx.x;
+  const int k = blockIdx.x * kEmdThreads + threadIdx.x;
   if (k >= n) return;
   const T* p1 = xyz1 + row_at(bb, n, k) * 3;
   const T x1 = p1[0], y1 = p1[1], z1 = p1[2];
@@ -241,18 +159,18 @@ __global__ void emd_grad1_fin_kernel(const T* __restrict__ part, int S, int b, i
 
 // grad2: one block per (l, b); lanes stride over k, block reduce (:285-323).
 template <typename T>
-__global__ void __launch_bounds__(kThreads)
+__global__ void __launch_bounds__(kEmdThreads)
     emd_grad2_kernel(const T* __restrict__ xyz1, const T* __restrict__ xyz2,
                      const T* __restrict__ match, const T* __restrict__ gcost, int n, int m,
                      T* __restrict__ grad2) {
-  __shared__ T red[kThreads / 64];
+  __shared__ T red[kEmdThreads / 64];
   const int l = blockIdx.x, bb = blockIdx.y;
   const T* p2 = xyz2 + ((size_t)bb * m + l) * 3;
   const T x2 = p2[0], y2 = p2[1], z2 = p2[2];
   const T* __restrict__ row = match + ((size_t)bb * m + l) * n;
   const T* __restrict__ pb = xyz1 + (size_t)bb * n * 3;
   T sx = 0, sy = 0, sz = 0;
-  for (int k = threadIdx.x; k < n; k += kThreads) {
+  for (int k = threadIdx.x; k < n; k += kEmdThreads) {
     const T d = row[k] * (T)2;
     sx = fmaT<T>(x2 - pb[3 * k], d, sx);
     sy = fmaT<T>(y2 - pb[3 * k + 1], d, sy);
@@ -276,8 +194,6 @@ __global__ void __launch_bounds__(kThreads)
 // pass walk the same (row k, column l) pairs, so they share one launch and one
 // d2 per pair: 21 pass launches + the pack + the match write (with the cost fused).
 // ---------------------------------------------------------------------------
-constexpr int kRowWaves = 16;  // column splits per block, one wave each
-
 // A point with the coefficient it carries into a pass (x, y, z, w = coef),
 // float4 / double4: a native vector type, so copies stay in registers.
 template <typename T>
@@ -320,8 +236,7 @@ __global__ void emd_pack_kernel(const T* __restrict__ xyz1, size_t bn, T multiL,
   }
 }
 
-constexpr int kColChunk = 128;  // columns per wave per LDS chunk (64 for PH 3: two packs)
-
+// a wave's LDS chunk: kColChunk = 128 columns (64 for PH 3: two packs)
 template <typename T, int PH>
 __device__ __forceinline__ T rowpass_chunk(const Col4<T>* __restrict__ st, int cnt, T x1, T y1,
                                            T z1, T rl, T lvl2, T acc) {
@@ -443,106 +358,11 @@ __global__ void __launch_bounds__(64 * kRowWaves)
 }
 
 // ---------------------------------------------------------------------------
-// Host side: one plan of the workspace, one prologue, four entries.
+// Host side: the plan (EmdPlan at d = 3), the prologue (emd_entry) and the
+// launch sequence (emd_run_levels) are emd_core.hpp's; four entries.
 // ---------------------------------------------------------------------------
-// Column splits of matchcost's and matchcost_bwd's partials: ~4 waves per SIMD.
-constexpr int emd_splits(int b, int n, int m) {
-  const long long rows = (long long)b * std::max(n, m);
-  const long long want_lanes = 4LL * kCUs * 4 * 64;
-  int s = (int)std::max(1LL, (want_lanes + rows - 1) / std::max(1LL, rows));
-  s = std::min(s, std::max(1, std::min(n, m) / 64));
-  return std::max(1, std::min(s, 32));
-}
-constexpr size_t blocks_of(int count, int per) {
-  return (size_t)((std::max(count, 1) + per - 1) / per);
-}
-
-// The workspace of every pcfm_emd_* entry as offsets in elements of T.  The
-// regions of approxmatch follow one another, each starting where the one
-// before it ends.  The Col4 packs come first and each is a whole number of
-// Col4 (4 elements), so they are aligned whenever ws itself is aligned to
-// sizeof(Col4<T>) = 16 B (f32) / 32 B (f64), which every device allocation is
-// -- whatever else the workspace holds.  matchcost and matchcost_bwd use
-// nothing but their block partials, which therefore start at 0.
 static_assert(sizeof(Col4<float>) == 4 * sizeof(float) &&
               sizeof(Col4<double>) == 4 * sizeof(double));
-struct EmdPlan {
-  int S = 1;  // emd_splits
-  size_t bn = 0, bm = 0;
-  size_t packK = 0, packL0 = 0, packL1 = 0;  // Col4 [bn], [bm], [bm]
-  size_t remL = 0;                           // [bn]
-  size_t levL = 0, levR = 0;                 // [kLevels][bn], [kLevels][bm]
-  size_t mpart = 0, mpart_elems = 0;         // emd_match_cost_kernel's block partials
-  size_t part = 0, part_elems = 0;           // emd_cost_kernel's / emd_grad1_kernel's partials
-  size_t total = 0, bytes = 0;
-
-  constexpr EmdPlan(int b, int n, int m, size_t elem_bytes)
-      : S(emd_splits(b, n, m)), bn((size_t)b * n), bm((size_t)b * m) {
-    const size_t kblocks = blocks_of(n, kThreads);
-    mpart_elems = b * blocks_of(m, kMatchL) * kblocks;
-    part_elems = std::max((size_t)b * S * kblocks, (size_t)S * bn * 3);
-    size_t end = 0;
-    for (auto [region, elems] : {std::pair<size_t*, size_t>{&packK, 4 * bn},
-                                 {&packL0, 4 * bm},
-                                 {&packL1, 4 * bm},
-                                 {&remL, bn},
-                                 {&levL, kLevels * bn},
-                                 {&levR, kLevels * bm},
-                                 {&mpart, mpart_elems}}) {
-      *region = end;
-      end += elems;
-    }
-    total = std::max(end, part + part_elems);
-    bytes = total * elem_bytes;
-  }
-};
-
-// the packs aligned, and the total the end of whichever region ends last
-constexpr bool emd_plan_ok() {
-  constexpr int sizes[] = {0, 1, 37, 64, 513, 2048, 20000};
-  for (int b : sizes)
-    for (int n : sizes)
-      for (int m : sizes)
-        for (size_t e : {(size_t)4, (size_t)8}) {
-          const EmdPlan p(b, n, m, e);
-          if (p.packK % 4 != 0 || p.packL0 % 4 != 0 || p.packL1 % 4 != 0) return false;
-          if (p.total != std::max(p.mpart + p.mpart_elems, p.part + p.part_elems)) return false;
-          if (p.bytes != p.total * e) return false;
-        }
-  return true;
-}
-static_assert(emd_plan_ok(), "EmdPlan: packs unaligned, or the total is not the last region's end");
-
-template <typename T>
-using EmdOut = std::pair<T*, size_t>;  // an output and its element count
-
-// The prologue of the four entries: argument and workspace checks, then either
-// launch(plan, ws) or, for an empty problem, the outputs zero-filled.
-template <typename T, typename Launch>
-int emd_entry(const char* who, int b, int n, int m, void* ws, size_t ws_bytes, hipStream_t st,
-              std::initializer_list<EmdOut<T>> outs, Launch&& launch) {
-  PCFM_CHECK_ARG(b >= 0 && n >= 0 && m >= 0, "%s: negative size", who);
-  const EmdPlan p(b, n, m, sizeof(T));
-  PCFM_CHECK_ARG(ws_bytes >= p.bytes, "%s: workspace %zu < %zu bytes", who, ws_bytes, p.bytes);
-  if (b == 0) return PCFM_OK;
-  if (n != 0 && m != 0) {
-    launch(p, (T*)ws);
-    return check_launch(who);
-  }
-  for (const EmdOut<T>& o : outs) {
-    if (o.first == nullptr || o.second == 0) continue;
-    const hipError_t e = hipMemsetAsync(o.first, 0, o.second * sizeof(T), st);
-    if (e != hipSuccess) {
-      set_error("%s: hipMemsetAsync: %s", who, hipGetErrorString(e));
-      return (int)e;
-    }
-  }
-  return PCFM_OK;
-}
-
-inline dim3 grid1d(size_t total, int threads = 256) {
-  return dim3(ceil_div((long long)std::max<size_t>(total, 1), threads));
-}
 
 // The 21 pass launches, then match (when non-null) and, when cost is non-null,
 // the fused matchcost.  PCFM_EMD_FORM=unfused runs PH 2 and the next level's
@@ -559,23 +379,14 @@ void launch_approxmatch(const T* xyz1, const T* xyz2, int b, int n, int m, T* ma
                      p.bn, multiL, xyz2, p.bm, multiR, s);
   const dim3 gL(ceil_div(n, 64), b), gR(ceil_div(m, 64), b), blk(64 * kRowWaves);
   auto lv2 = [](int j) { return (T)level_log2e(j); };
-  const char* form = std::getenv("PCFM_EMD_FORM");
-  const bool fused = form == nullptr || form[0] != 'u';
-  hipLaunchKernelGGL((emd_rowpass_kernel<T, 0>), gL, blk, 0, st, n, m, lv2(0), (T)0, 0, s);
-  for (int j = 0; j < kLevels; ++j) {
-    hipLaunchKernelGGL((emd_rowpass_kernel<T, 1>), gR, blk, 0, st, m, n, lv2(j), (T)0, j, s);
-    if (fused && j + 1 < kLevels) {
-      hipLaunchKernelGGL((emd_rowpass_kernel<T, 3>), gL, blk, 0, st, n, m, lv2(j), lv2(j + 1), j,
-                         s);
-    } else {
-      hipLaunchKernelGGL((emd_rowpass_kernel<T, 2>), gL, blk, 0, st, n, m, lv2(j), (T)0, j, s);
-      if (j + 1 < kLevels)
-        hipLaunchKernelGGL((emd_rowpass_kernel<T, 0>), gL, blk, 0, st, n, m, lv2(j + 1), (T)0,
-                           j + 1, s);
-    }
-  }
-  const dim3 gm(ceil_div(n, kThreads), ceil_div(m, kMatchL), b);
-  hipLaunchKernelGGL(emd_match_cost_kernel<T>, gm, dim3(kThreads), 0, st, xyz1, xyz2, b, n, m,
+  emd_run_levels([&](auto ph, int j, int jn) {
+    constexpr int PH = decltype(ph)::value;
+    constexpr bool rows_k = PH != 1;  // PH 1's rows are the l points
+    hipLaunchKernelGGL((emd_rowpass_kernel<T, PH>), rows_k ? gL : gR, blk, 0, st, rows_k ? n : m,
+                       rows_k ? m : n, lv2(j), PH == 3 ? lv2(jn) : (T)0, j, s);
+  });
+  const dim3 gm(ceil_div(n, kEmdThreads), ceil_div(m, kMatchL), b);
+  hipLaunchKernelGGL(emd_match_cost_kernel<T>, gm, dim3(kEmdThreads), 0, st, xyz1, xyz2, b, n, m,
                      (const T*)s.levL, (const T*)s.levR, match, ws + p.mpart);
   if (cost != nullptr)
     hipLaunchKernelGGL(emd_cost_fin_kernel<T>, dim3(b), dim3(64), 0, st, (const T*)(ws + p.mpart),
@@ -585,7 +396,7 @@ void launch_approxmatch(const T* xyz1, const T* xyz2, int b, int n, int m, T* ma
 template <typename T>
 int approxmatch(const T* xyz1, const T* xyz2, int b, int n, int m, T* match, void* ws,
                 size_t ws_bytes, hipStream_t st) {
-  return emd_entry<T>("approxmatch", b, n, m, ws, ws_bytes, st, {}, [&](const EmdPlan& p, T* w) {
+  return emd_entry<T>("approxmatch", b, n, m, 3, ws, ws_bytes, st, {}, [&](const EmdPlan& p, T* w) {
     launch_approxmatch<T>(xyz1, xyz2, b, n, m, match, nullptr, p, w, st);
   });
 }
@@ -596,7 +407,7 @@ template <typename T>
 int approxmatch_cost(const T* xyz1, const T* xyz2, int b, int n, int m, T* match, T* cost,
                      void* ws, size_t ws_bytes, hipStream_t st) {
   PCFM_CHECK_ARG(cost != nullptr, "approxmatch_cost: cost is required");
-  return emd_entry<T>("approxmatch_cost", b, n, m, ws, ws_bytes, st, {{cost, (size_t)b}},
+  return emd_entry<T>("approxmatch_cost", b, n, m, 3, ws, ws_bytes, st, {{cost, (size_t)b}},
                       [&](const EmdPlan& p, T* w) {
                         launch_approxmatch<T>(xyz1, xyz2, b, n, m, match, cost, p, w, st);
                       });
@@ -605,10 +416,10 @@ int approxmatch_cost(const T* xyz1, const T* xyz2, int b, int n, int m, T* match
 template <typename T>
 int matchcost(const T* xyz1, const T* xyz2, const T* match, int b, int n, int m, T* cost,
               void* ws, size_t ws_bytes, hipStream_t st) {
-  return emd_entry<T>("matchcost", b, n, m, ws, ws_bytes, st, {{cost, (size_t)b}},
+  return emd_entry<T>("matchcost", b, n, m, 3, ws, ws_bytes, st, {{cost, (size_t)b}},
                       [&](const EmdPlan& p, T* w) {
-                        const dim3 g(ceil_div(n, kThreads), p.S, b);
-                        hipLaunchKernelGGL(emd_cost_kernel<T>, g, dim3(kThreads), 0, st, xyz1,
+                        const dim3 g(ceil_div(n, kEmdThreads), p.S, b);
+                        hipLaunchKernelGGL(emd_cost_kernel<T>, g, dim3(kEmdThreads), 0, st, xyz1,
                                            xyz2, match, b, n, m, p.S, w + p.part);
                         hipLaunchKernelGGL(emd_cost_fin_kernel<T>, dim3(b), dim3(64), 0, st,
                                            (const T*)(w + p.part), p.S * (int)g.x, cost);
@@ -619,13 +430,13 @@ template <typename T>
 int matchcost_bwd(const T* gcost, const T* xyz1, const T* xyz2, const T* match, int b, int n,
                   int m, T* grad1, T* grad2, void* ws, size_t ws_bytes, hipStream_t st) {
   return emd_entry<T>(
-      "matchcost_bwd", b, n, m, ws, ws_bytes, st,
+      "matchcost_bwd", b, n, m, 3, ws, ws_bytes, st,
       {{grad1, (size_t)b * n * 3}, {grad2, (size_t)b * m * 3}}, [&](const EmdPlan& p, T* w) {
-        hipLaunchKernelGGL(emd_grad1_kernel<T>, dim3(ceil_div(n, kThreads), p.S, b),
-                           dim3(kThreads), 0, st, xyz1, xyz2, match, b, n, m, p.S, w + p.part);
+        hipLaunchKernelGGL(emd_grad1_kernel<T>, dim3(ceil_div(n, kEmdThreads), p.S, b),
+                           dim3(kEmdThreads), 0, st, xyz1, xyz2, match, b, n, m, p.S, w + p.part);
         hipLaunchKernelGGL(emd_grad1_fin_kernel<T>, grid1d(p.bn * 3), dim3(256), 0, st,
                            (const T*)(w + p.part), p.S, b, n, gcost, grad1);
-        hipLaunchKernelGGL(emd_grad2_kernel<T>, dim3(m, b), dim3(kThreads), 0, st, xyz1, xyz2,
+        hipLaunchKernelGGL(emd_grad2_kernel<T>, dim3(m, b), dim3(kEmdThreads), 0, st, xyz1, xyz2,
                            match, gcost, n, m, grad2);
       });
 }
@@ -637,7 +448,7 @@ using namespace pcfm;
 
 extern "C" size_t pcfm_emd_workspace_bytes(int b, int n, int m, int elem_bytes) {
   if (b < 0 || n < 0 || m < 0 || (elem_bytes != 4 && elem_bytes != 8)) return 0;
-  return EmdPlan(b, n, m, (size_t)elem_bytes).bytes;
+  return EmdPlan(b, n, m, 3, (size_t)elem_bytes).bytes;
 }
 
 extern "C" int pcfm_emd_approxmatch_f32(const float* xyz1, const float* xyz2, int b, int n, int m,

@@ -205,6 +205,20 @@ OCCUPANCY_SIGNATURES = {
 
 OCCUPANCY_ABI_VERSION = 1
 
+# name -> (restype, argtypes); every symbol of include/pcfm_emd_nd.h (the
+# approximate EMD over D-component points: a fifth sibling header with its own
+# version, disjoint from the five tables above)
+EMD_ND_SIGNATURES = {
+    "pcfm_emd_nd_abi_version": (_I, []),
+    "pcfm_emd_nd_supported": (_I, [_I]),
+    "pcfm_emd_nd_workspace_bytes": (_Z, [_I, _I, _I, _I]),
+    "pcfm_emd_nd_approxmatch_cost_f32": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+    "pcfm_emd_nd_matchcost_f32": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "pcfm_emd_nd_matchcost_bwd_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _Z, _P]),
+}
+
+EMD_ND_ABI_VERSION = 1
+
 _lock = threading.Lock()
 _lib = None
 
@@ -227,7 +241,7 @@ def load() -> ctypes.CDLL:
                     "(HIP tensors have no fallback)")
             lib = ctypes.CDLL(LIB_PATH)
             for table in (SIGNATURES, ND_SIGNATURES, CROSS_SIGNATURES, FPS_SIGNATURES,
-                          OCCUPANCY_SIGNATURES):
+                          OCCUPANCY_SIGNATURES, EMD_ND_SIGNATURES):
                 for name, (res, args) in table.items():
                     fn = getattr(lib, name)
                     fn.restype = res
@@ -251,6 +265,10 @@ def load() -> ctypes.CDLL:
             if v != OCCUPANCY_ABI_VERSION:
                 raise RuntimeError(f"pcfm: occupancy ABI version {v} != expected "
                                    f"{OCCUPANCY_ABI_VERSION}; rebuild")
+            v = lib.pcfm_emd_nd_abi_version()
+            if v != EMD_ND_ABI_VERSION:
+                raise RuntimeError(f"pcfm: emd_nd ABI version {v} != expected "
+                                   f"{EMD_ND_ABI_VERSION}; rebuild")
             _lib = lib
     return _lib
 

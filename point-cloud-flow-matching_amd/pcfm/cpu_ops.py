@@ -33,6 +33,7 @@ __all__ = [
     "chamfer_forward", "chamfer_backward", "approxmatch_forward", "matchcost_forward",
     "matchcost_backward", "chamfer_nd_forward", "chamfer_nd_backward", "chamfer_cross_forward",
     "farthest_point_sample", "occupancy_nodes", "occupancy_counts",
+    "approxmatch_forward_nd", "matchcost_forward_nd", "matchcost_backward_nd",
 ]
 
 # rows of the query set per pairwise block (bounds the (rows, M) temporaries)
@@ -409,9 +410,19 @@ def _pair_sqdist(xyz1, xyz2):
     return _sqdist(d[..., 0], d[..., 1], d[..., 2])
 
 
+def _pair_sqdist_nd(p1, p2):
+    """(b, n, m) squared distances over all D components, d = p2 - p1, as the
+    chain of _sqdist_nd (include/pcfm_emd_nd.h); at D = 3 the bits of _pair_sqdist."""
+    return _sqdist_nd(p2[:, None, :, :] - p1[:, :, None, :])
+
+
 def approxmatch_forward(xyz1: torch.Tensor, xyz2: torch.Tensor) -> torch.Tensor:
     """approxmatch: 10 levels (level = -4^j, j = 7..-2, the last 0) of soft
     matching; -> match (b, m, n)."""
+    return _approxmatch(xyz1, xyz2, _pair_sqdist)
+
+
+def _approxmatch(xyz1, xyz2, pair_sqdist):
     b, n = xyz1.shape[0], xyz1.shape[1]
     m = xyz2.shape[1]
     dt = xyz1.dtype
@@ -420,7 +431,7 @@ def approxmatch_forward(xyz1: torch.Tensor, xyz2: torch.Tensor) -> torch.Tensor:
         return match.transpose(1, 2).contiguous()
     multi_l = 1.0 if n >= m else float(m // n)
     multi_r = float(n // m) if n >= m else 1.0
-    d2 = _pair_sqdist(xyz1, xyz2)
+    d2 = pair_sqdist(xyz1, xyz2)
     rem_l = torch.full((b, n), multi_l, dtype=dt)
     rem_r = torch.full((b, m), multi_r, dtype=dt)
     for j in range(7, -3, -1):
@@ -452,3 +463,24 @@ def matchcost_backward(grad_cost: torch.Tensor, xyz1: torch.Tensor, xyz2: torch.
     g1 = (mt.sum(dim=2)[:, :, None] * xyz1 - torch.bmm(mt, xyz2)) * g
     g2 = (mt.sum(dim=1)[:, :, None] * xyz2 - torch.bmm(mt.transpose(1, 2), xyz1)) * g
     return [g1, g2]
+
+
+# the same three over D-component points (include/pcfm_emd_nd.h, csrc/emd_nd.hip):
+# every component enters the squared distance with the same weight
+def approxmatch_forward_nd(p1: torch.Tensor, p2: torch.Tensor) -> torch.Tensor:
+    """approxmatch over p1 (b, n, D), p2 (b, m, D), D >= 2 -> match (b, m, n); at
+    D = 3 the bits of approxmatch_forward."""
+    return _approxmatch(p1, p2, _pair_sqdist_nd)
+
+
+def matchcost_forward_nd(p1: torch.Tensor, p2: torch.Tensor, match: torch.Tensor):
+    """cost[b] = sum_{k,l} d2(k, l) * match[b, l, k], d2 over all D components."""
+    d2 = _pair_sqdist_nd(p1, p2)  # (b, n, m)
+    return (d2 * match.transpose(1, 2)).sum(dim=(1, 2))
+
+
+def matchcost_backward_nd(grad_cost: torch.Tensor, p1: torch.Tensor, p2: torch.Tensor,
+                          match: torch.Tensor):
+    """matchcost_backward, whose closed form does not look at D: -> [grad1 (b, n, D),
+    grad2 (b, m, D)]."""
+    return matchcost_backward(grad_cost, p1, p2, match)

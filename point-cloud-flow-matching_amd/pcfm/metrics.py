@@ -9,7 +9,10 @@ Each of the first three reduces an (S, R) matrix of cloud-to-cloud distances:
     (csrc/chamfer_cross.hip through ops.chamfer_cross_forward): no cloud is
     copied and no per-point distance is written;
   * pairwise_emd -- the approximate-match cost of PyTorchEMD over gathered
-    chunks of pairs (ops.approxmatch_cost_forward, no match matrix written).
+    chunks of pairs (ops.approxmatch_cost_forward, no match matrix written);
+  * pairwise_emd_nd -- the same over all D components of the points
+    (ops.approxmatch_cost_forward_nd, csrc/emd_nd.hip), so that the EMD figures
+    see the colour of xyz+rgb clouds.
 
 Clouds larger than the matrices can take (or of different sizes) are first cut
 to n_points points each by farthest-point sampling: subsample, one launch of
@@ -31,8 +34,8 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["pairwise_chamfer", "pairwise_emd", "mmd_cov", "one_nna", "generation_metrics",
-           "subsample", "occupancy_counts", "jsd_from_counts", "jsd"]
+__all__ = ["pairwise_chamfer", "pairwise_emd", "pairwise_emd_nd", "mmd_cov", "one_nna",
+           "generation_metrics", "subsample", "occupancy_counts", "jsd_from_counts", "jsd"]
 
 # pairs per approxmatch call, at most (the batch is a grid dimension of its kernels)
 _EMD_MAX_PAIRS = 32767
@@ -72,16 +75,32 @@ def _emd_chunk_bytes(pairs: int, n: int, m: int, like: torch.Tensor) -> int:
     return inputs + 4 * pairs * n * m * 4
 
 
-def _emd_pairs_per_chunk(total: int, n: int, m: int, max_bytes: int, like: torch.Tensor) -> int:
+def _emd_nd_chunk_bytes(pairs: int, n: int, m: int, d: int, like: torch.Tensor) -> int:
+    """_emd_chunk_bytes for points of d components: the gathered inputs and the
+    workspace of include/pcfm_emd_nd.h (HIP), which grows with the pack width."""
+    inputs = pairs * (n + m) * d * 4
+    if like.is_cuda:
+        return inputs + _lib.query("pcfm_emd_nd_workspace_bytes", pairs, n, m, d)
+    return inputs + 4 * pairs * n * m * 4
+
+
+def _emd_pairs_per_chunk(total: int, n: int, m: int, max_bytes: int, like: torch.Tensor,
+                         d=None) -> int:
     """Pairs per chunk (<= total, <= _EMD_MAX_PAIRS): the largest count a bisection
-    finds whose bytes stay under max_bytes."""
-    if _emd_chunk_bytes(1, n, m, like) > max_bytes:
+    finds whose bytes stay under max_bytes.  d: the N-D entries' component count
+    (None: pairwise_emd's 3-D entries)."""
+    def chunk_bytes(pairs):
+        if d is None:
+            return _emd_chunk_bytes(pairs, n, m, like)
+        return _emd_nd_chunk_bytes(pairs, n, m, d, like)
+
+    if chunk_bytes(1) > max_bytes:
         raise ValueError(f"pairwise_emd: max_bytes = {max_bytes} is below one pair's "
-                         f"{_emd_chunk_bytes(1, n, m, like)} bytes")
+                         f"{chunk_bytes(1)} bytes")
     lo, hi = 1, max(1, min(total, _EMD_MAX_PAIRS))   # bytes grow with the pair count
     while lo < hi:
         mid = (lo + hi + 1) // 2
-        if _emd_chunk_bytes(mid, n, m, like) <= max_bytes:
+        if chunk_bytes(mid) <= max_bytes:
             lo = mid
         else:
             hi = mid - 1
@@ -118,6 +137,42 @@ def pairwise_emd(x: torch.Tensor, y: torch.Tensor, max_bytes: int = 1 << 30) -> 
         p = torch.arange(p0, min(p0 + chunk, s * r), device=x.device)
         i, j = torch.div(p, r, rounding_mode="floor"), p % r
         _, cost = ops.approxmatch_cost_forward(x[i], y[j], want_match=False)
+        out[p0:p0 + p.numel()] = cost / n
+    return out.view(s, r)
+
+
+@torch.no_grad()
+def pairwise_emd_nd(x: torch.Tensor, y: torch.Tensor, max_bytes: int = 1 << 30) -> torch.Tensor:
+    """x (S, n, D), y (R, n, D) float32, D in {2, 3, 5, 6} -> (S, R) float32:
+    pairwise_emd with the squared distance taken over all D components, every
+    component with the same weight (ops.approxmatch_cost_forward_nd); at D = 3 the
+    bits of pairwise_emd.
+
+    ORIENTATION: as for pairwise_emd, the approximate match is not symmetric in
+    its two clouds: the first argument's clouds are always p1, pairwise_emd_nd(y, x)
+    is not the transpose of pairwise_emd_nd(x, y), and nothing is symmetrised.
+
+    Pairs are gathered in chunks; a chunk's gathered inputs plus the call's
+    workspace stay under max_bytes.  The result does not depend on the chunking
+    (on HIP tensors by the kernels' contract: a pair's bits do not depend on the
+    batch it is in).  An unsupported or unequal D and unequal point counts raise
+    ValueError."""
+    if x.dim() != 3 or y.dim() != 3 or x.shape[2] != y.shape[2] \
+            or x.shape[2] not in ops.EMD_ND_DIMS:
+        raise ValueError(f"pairwise_emd_nd: expected (S, n, D) and (R, n, D), D in "
+                         f"{ops.EMD_ND_DIMS}, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"pairwise_emd_nd: point counts differ ({x.shape[1]} and {y.shape[1]})")
+    x, y = x.contiguous(), y.contiguous()
+    s, r, n, d = x.shape[0], y.shape[0], x.shape[1], x.shape[2]
+    out = torch.empty(s * r, dtype=torch.float32, device=x.device)
+    if s * r == 0 or n == 0:
+        return out.zero_().view(s, r)
+    chunk = _emd_pairs_per_chunk(s * r, n, n, max_bytes, x, d)
+    for p0 in range(0, s * r, chunk):
+        p = torch.arange(p0, min(p0 + chunk, s * r), device=x.device)
+        i, j = torch.div(p, r, rounding_mode="floor"), p % r
+        _, cost = ops.approxmatch_cost_forward_nd(x[i], y[j], want_match=False)
         out[p0:p0 + p.numel()] = cost / n
     return out.view(s, r)
 
@@ -254,11 +309,15 @@ def jsd(sample: torch.Tensor, ref: torch.Tensor, resolution: int = 28) -> torch.
 
 @torch.no_grad()
 def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True,
-                       n_points=None, jsd: bool = False, jsd_resolution: int = 28) -> dict:
+                       n_points=None, jsd: bool = False, jsd_resolution: int = 28,
+                       emd_components: str = "xyz") -> dict:
     """sample (S, N, D), ref (R, M, D) float32 -> {mmd_cd, mmd_smp_cd, cov_cd,
     1nna_cd, 1nna_gen_cd, 1nna_ref_cd} and, with emd=True, the same six with
-    _emd.  Chamfer runs over all D components (D in {2, 3, 5, 6}); EMD over the
-    first three (xyz) and needs N == M.  The S x S and R x R matrices of 1-NNA
+    _emd.  Chamfer runs over all D components (D in {2, 3, 5, 6}).  EMD needs
+    N == M and runs over what emd_components names: "xyz", the first three
+    components (pairwise_emd; D = 2 raises ValueError), or "all", all D components
+    with the same weight (pairwise_emd_nd; D = 2 works), under the same _emd keys.
+    Any other value raises ValueError.  The S x S and R x R matrices of 1-NNA
     come from the same kernels, a set against itself.  n_points: both sets go
     through subsample(., n_points) before any matrix is formed, so sets whose
     clouds differ in size (or are too large for the EMD matrix) compare at
@@ -271,6 +330,9 @@ def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True
     a shape, not where its points lie.  N and M may differ (the histograms are
     normalised); D = 2 raises ValueError.  With jsd=False the result is what it
     was without the keyword."""
+    if emd_components not in ("xyz", "all"):
+        raise ValueError(f"generation_metrics: emd_components = {emd_components!r} is neither "
+                         "'xyz' nor 'all'")
     extra = {"jsd": _jsd(sample, ref, jsd_resolution)} if jsd else {}
     if n_points is not None:
         sample, ref = subsample(sample, n_points), subsample(ref, n_points)
@@ -285,7 +347,9 @@ def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True
         return out
 
     out = reduce(pairwise_chamfer, sample, ref, "cd")
-    if emd:
+    if emd and emd_components == "all":
+        out.update(reduce(pairwise_emd_nd, sample, ref, "emd"))
+    elif emd:
         if sample.shape[-1] < 3 or ref.shape[-1] < 3:
             raise ValueError("generation_metrics: EMD needs at least three components (xyz)")
         out.update(reduce(pairwise_emd, sample[..., :3].contiguous(), ref[..., :3].contiguous(),

@@ -856,6 +856,84 @@ emd_cuda = types.SimpleNamespace(approxmatch_forward=approxmatch_forward,
                                  matchcost_backward=matchcost_backward)
 
 
+# --------------------------------------------------------------------------
+# the same over D-component points, D in {2, 3, 5, 6}, float32
+# (include/pcfm_emd_nd.h, csrc/emd_nd.hip); every component has the same weight
+# --------------------------------------------------------------------------
+EMD_ND_DIMS = (2, 3, 5, 6)
+
+
+def _emd_nd_check(p1, p2, match=None, grad_cost=None):
+    """-> (b, n, m, d) of p1 (B, N, D), p2 (B, M, D) float32 contiguous; match
+    (B, M, N) and grad_cost (B,) likewise where given."""
+    for name, t in (("p1", p1), ("p2", p2), ("match", match), ("grad_cost", grad_cost)):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"emd_nd: {name} must be float32, got {t.dtype}")
+        _check_contig(t, name)
+    if p1.dim() != 3 or p2.dim() != 3 or p1.shape[0] != p2.shape[0] or p1.shape[2] != p2.shape[2]:
+        raise RuntimeError(f"emd_nd: expected (B,N,D) and (B,M,D), got {tuple(p1.shape)} and "
+                           f"{tuple(p2.shape)}")
+    b, n, d = p1.shape
+    m = p2.shape[1]
+    if d not in EMD_ND_DIMS:
+        raise RuntimeError(f"emd_nd: D = {d} is not one of {EMD_ND_DIMS}")
+    if match is not None and tuple(match.shape) != (b, m, n):
+        raise RuntimeError(f"emd_nd: expected match {(b, m, n)}, got {tuple(match.shape)}")
+    if grad_cost is not None and tuple(grad_cost.shape) != (b,):
+        raise RuntimeError(f"emd_nd: expected grad_cost {(b,)}, got {tuple(grad_cost.shape)}")
+    return b, n, m, d
+
+
+def _emd_nd_workspace(b, n, m, d, like):
+    return _workspace(_lib.query("pcfm_emd_nd_workspace_bytes", b, n, m, d), like)
+
+
+def approxmatch_cost_forward_nd(p1: torch.Tensor, p2: torch.Tensor, want_match: bool = True):
+    """approxmatch + matchcost over all D components in one native call: p1
+    (B, N, D), p2 (B, M, D) float32 -> (match (B, M, N) or None, cost (B,)).  The
+    cost is summed from the match kernel's own values; want_match=False skips
+    writing match.  At D = 3 the bits of approxmatch_cost_forward."""
+    b, n, m, d = _emd_nd_check(p1, p2)
+    if _host(p1, p2):
+        match = cpu_ops.approxmatch_forward_nd(p1, p2)
+        return (match if want_match else None), cpu_ops.matchcost_forward_nd(p1, p2, match)
+    ws = _emd_nd_workspace(b, n, m, d, p1)
+    match = torch.empty((b, m, n), dtype=p1.dtype, device=p1.device) if want_match else None
+    cost = torch.empty((b,), dtype=p1.dtype, device=p1.device)
+    _lib.call("pcfm_emd_nd_approxmatch_cost_f32", _ptr(p1), _ptr(p2), b, n, m, d,
+              _ptr(match) if match is not None else None, _ptr(cost), _ptr(ws), ws.numel(),
+              _stream(p1))
+    return match, cost
+
+
+def matchcost_forward_nd(p1: torch.Tensor, p2: torch.Tensor, match: torch.Tensor):
+    """-> cost (B,) = sum_{k,l} d2(k, l) * match[l, k], d2 over all D components."""
+    b, n, m, d = _emd_nd_check(p1, p2, match)
+    if _host(p1, p2, match):
+        return cpu_ops.matchcost_forward_nd(p1, p2, match)
+    ws = _emd_nd_workspace(b, n, m, d, p1)
+    cost = torch.empty((b,), dtype=p1.dtype, device=p1.device)
+    _lib.call("pcfm_emd_nd_matchcost_f32", _ptr(p1), _ptr(p2), _ptr(match), b, n, m, d,
+              _ptr(cost), _ptr(ws), ws.numel(), _stream(p1))
+    return cost
+
+
+def matchcost_backward_nd(grad_cost: torch.Tensor, p1: torch.Tensor, p2: torch.Tensor,
+                          match: torch.Tensor):
+    """-> [grad1 (B, N, D), grad2 (B, M, D)] of matchcost_forward_nd for grad_cost (B,)."""
+    b, n, m, d = _emd_nd_check(p1, p2, match, grad_cost)
+    if _host(grad_cost, p1, p2, match):
+        return cpu_ops.matchcost_backward_nd(grad_cost, p1, p2, match)
+    ws = _emd_nd_workspace(b, n, m, d, p1)
+    g1 = torch.empty((b, n, d), dtype=p1.dtype, device=p1.device)
+    g2 = torch.empty((b, m, d), dtype=p1.dtype, device=p1.device)
+    _lib.call("pcfm_emd_nd_matchcost_bwd_f32", _ptr(grad_cost), _ptr(p1), _ptr(p2), _ptr(match),
+              b, n, m, d, _ptr(g1), _ptr(g2), _ptr(ws), ws.numel(), _stream(p1))
+    return [g1, g2]
+
+
 def host_routed(ext, host, names):
     """A binding namespace that calls the torch C++ extension `ext` (HIP tensors
     only: csrc/torch_backend.cpp, torch_losses.cpp) and sends a call whose tensor
