@@ -219,6 +219,18 @@ EMD_ND_SIGNATURES = {
 
 EMD_ND_ABI_VERSION = 1
 
+# name -> (restype, argtypes); every symbol of include/pcfm_emd_auction.h (the
+# assignment EMD by auction: a sixth sibling header with its own version, disjoint
+# from the six tables above)
+EMD_AUCTION_SIGNATURES = {
+    "pcfm_emd_auction_abi_version": (_I, []),
+    "pcfm_emd_auction_max_points": (_I, [_I]),
+    "pcfm_emd_auction_workspace_bytes": (_Z, [_I, _I, _I]),
+    "pcfm_emd_auction_f32": (_I, [_P, _P, _I, _I, _I, _F, _I, _P, _P, _P, _P, _Z, _P]),
+}
+
+EMD_AUCTION_ABI_VERSION = 1
+
 _lock = threading.Lock()
 _lib = None
 
@@ -241,7 +253,7 @@ def load() -> ctypes.CDLL:
                     "(HIP tensors have no fallback)")
             lib = ctypes.CDLL(LIB_PATH)
             for table in (SIGNATURES, ND_SIGNATURES, CROSS_SIGNATURES, FPS_SIGNATURES,
-                          OCCUPANCY_SIGNATURES, EMD_ND_SIGNATURES):
+                          OCCUPANCY_SIGNATURES, EMD_ND_SIGNATURES, EMD_AUCTION_SIGNATURES):
                 for name, (res, args) in table.items():
                     fn = getattr(lib, name)
                     fn.restype = res
@@ -269,6 +281,10 @@ def load() -> ctypes.CDLL:
             if v != EMD_ND_ABI_VERSION:
                 raise RuntimeError(f"pcfm: emd_nd ABI version {v} != expected "
                                    f"{EMD_ND_ABI_VERSION}; rebuild")
+            v = lib.pcfm_emd_auction_abi_version()
+            if v != EMD_AUCTION_ABI_VERSION:
+                raise RuntimeError(f"pcfm: emd_auction ABI version {v} != expected "
+                                   f"{EMD_AUCTION_ABI_VERSION}; rebuild")
             _lib = lib
     return _lib
 

@@ -33,7 +33,7 @@ __all__ = [
     "chamfer_forward", "chamfer_backward", "approxmatch_forward", "matchcost_forward",
     "matchcost_backward", "chamfer_nd_forward", "chamfer_nd_backward", "chamfer_cross_forward",
     "farthest_point_sample", "occupancy_nodes", "occupancy_counts",
-    "approxmatch_forward_nd", "matchcost_forward_nd", "matchcost_backward_nd",
+    "approxmatch_forward_nd", "matchcost_forward_nd", "matchcost_backward_nd", "emd_auction",
 ]
 
 # rows of the query set per pairwise block (bounds the (rows, M) temporaries)
@@ -484,3 +484,86 @@ def matchcost_backward_nd(grad_cost: torch.Tensor, p1: torch.Tensor, p2: torch.T
     """matchcost_backward, whose closed form does not look at D: -> [grad1 (b, n, D),
     grad2 (b, m, D)]."""
     return matchcost_backward(grad_cost, p1, p2, match)
+
+
+# ---------------------------------------------------------------------------
+# assignment EMD by auction (include/pcfm_emd_auction.h, csrc/emd_auction.hip)
+# ---------------------------------------------------------------------------
+def _auction_pair(c: torch.Tensor, eps_rel: float, max_rounds: int):
+    """One pair of the rule of include/pcfm_emd_auction.h on its (n, n) float32 cost
+    matrix, n >= 1 -> (assignment (n,) int64, rounds), or (None, -1) for a pair
+    that would need a round beyond max_rounds.  Every step is an elementwise
+    float32 operation or a maximum, over all bidders of a round at once."""
+    n = c.shape[0]
+    cmax = torch.where(torch.isnan(c), torch.zeros((), dtype=c.dtype), c).max()
+    if float(cmax) == 0.0:
+        return torch.arange(n), 0
+    eps_final = torch.tensor(eps_rel, dtype=torch.float32) * cmax
+    eps = torch.maximum(eps_final, cmax * 0.5)
+    price = torch.zeros(n, dtype=torch.float32)
+    neg_c = -c
+    low32 = 0xFFFFFFFF
+    rounds = 0
+    while True:                                     # phases
+        owner = torch.full((n,), -1, dtype=torch.long)
+        assigned = torch.full((n,), -1, dtype=torch.long)
+        while True:                                 # rounds
+            bidders = (assigned < 0).nonzero()[:, 0]
+            u = bidders.numel()
+            if u == 0:
+                break
+            if rounds == max_rounds:
+                return None, -1
+            rounds += 1
+            v = neg_c[bidders] - price[None, :]     # (u, n)
+            v1, j1 = v.max(dim=1)                   # the first maximum: the lowest index
+            if n == 1:
+                v2 = v1
+            else:
+                v[torch.arange(u), j1] = float("-inf")
+                v2 = v.max(dim=1).values
+            pj = price[j1]
+            bid = pj + ((v1 - v2) + eps)
+            up = torch.nextafter(pj, torch.full_like(pj, float("inf")))
+            bid = torch.where(bid > pj, bid, up)
+            # the highest bid, the lowest person among equals: one max of
+            # (float bits of the bid) << 32 | ~person (bids are >= +0)
+            key = (bid.view(torch.int32).long() << 32) | (low32 - bidders)
+            best = torch.full((n,), -1, dtype=torch.long)
+            best.scatter_reduce_(0, j1, key, "amax", include_self=True)
+            objs = (best >= 0).nonzero()[:, 0]
+            won = best[objs]
+            winner = low32 - (won & low32)
+            prev = owner[objs]
+            assigned[prev[prev >= 0]] = -1
+            owner[objs] = winner
+            assigned[winner] = objs
+            price[objs] = (won >> 32).to(torch.int32).view(torch.float32)
+        if bool(eps == eps_final):
+            return assigned, rounds
+        eps = torch.maximum(eps_final, eps * 0.25)
+
+
+def emd_auction(p1: torch.Tensor, p2: torch.Tensor, eps_rel: float = 2.0 ** -16,
+                max_rounds: int = 1 << 20):
+    """The rule of include/pcfm_emd_auction.h in pure PyTorch: p1, p2 (B, n, D)
+    float32 -> (assignment (B, n) int32, cost (B,) float32, rounds (B,) int32).
+    The costs are the chain of _sqdist_nd (its fused multiply-adds by _fma32).  A
+    pair that does not finish within max_rounds has rounds -1, an assignment row
+    of -1 and a NaN cost."""
+    b, n, _ = p1.shape
+    assignment = torch.full((b, n), -1, dtype=torch.int32)
+    cost = torch.zeros(b, dtype=torch.float32)
+    rounds = torch.zeros(b, dtype=torch.int32)
+    if n == 0:
+        return assignment, cost, rounds
+    for bb in range(b):
+        c = _pair_sqdist_nd(p1[bb:bb + 1], p2[bb:bb + 1])[0]
+        a, r = _auction_pair(c, float(eps_rel), int(max_rounds))
+        rounds[bb] = r
+        if a is None:
+            cost[bb] = float("nan")
+            continue
+        assignment[bb] = a.to(torch.int32)
+        cost[bb] = c[torch.arange(n), a].double().sum().float()
+    return assignment, cost, rounds

@@ -1,7 +1,8 @@
 """Generation metrics between a set of generated clouds and a set of reference
 clouds: minimum matching distance (MMD), coverage (COV) and 1-nearest-neighbour
-accuracy (1-NNA), under Chamfer distance and under the approximate EMD, and the
-Jensen-Shannon divergence (JSD) between the two sets' occupancy histograms.
+accuracy (1-NNA), under Chamfer distance and under the EMD (the approximate match
+or the auction's one-to-one match), and the Jensen-Shannon divergence (JSD)
+between the two sets' occupancy histograms.
 
 Each of the first three reduces an (S, R) matrix of cloud-to-cloud distances:
 
@@ -12,7 +13,10 @@ Each of the first three reduces an (S, R) matrix of cloud-to-cloud distances:
     chunks of pairs (ops.approxmatch_cost_forward, no match matrix written);
   * pairwise_emd_nd -- the same over all D components of the points
     (ops.approxmatch_cost_forward_nd, csrc/emd_nd.hip), so that the EMD figures
-    see the colour of xyz+rgb clouds.
+    see the colour of xyz+rgb clouds;
+  * pairwise_emd_auction -- the cost of a one-to-one match within a stated bound
+    of the optimal bijection's (ops.emd_auction, csrc/emd_auction.hip), over all D
+    components: symmetric in its two clouds to within that bound.
 
 Clouds larger than the matrices can take (or of different sizes) are first cut
 to n_points points each by farthest-point sampling: subsample, one launch of
@@ -34,8 +38,9 @@ import torch
 
 from . import _lib, ops
 
-__all__ = ["pairwise_chamfer", "pairwise_emd", "pairwise_emd_nd", "mmd_cov", "one_nna",
-           "generation_metrics", "subsample", "occupancy_counts", "jsd_from_counts", "jsd"]
+__all__ = ["pairwise_chamfer", "pairwise_emd", "pairwise_emd_nd", "pairwise_emd_auction", "mmd_cov",
+           "one_nna", "generation_metrics", "subsample", "occupancy_counts", "jsd_from_counts",
+           "jsd"]
 
 # pairs per approxmatch call, at most (the batch is a grid dimension of its kernels)
 _EMD_MAX_PAIRS = 32767
@@ -177,6 +182,58 @@ def pairwise_emd_nd(x: torch.Tensor, y: torch.Tensor, max_bytes: int = 1 << 30) 
     return out.view(s, r)
 
 
+@torch.no_grad()
+def pairwise_emd_auction(x: torch.Tensor, y: torch.Tensor, eps_rel: float = 2.0 ** -16,
+                         max_rounds: int = 1 << 20, max_bytes: int = 1 << 30) -> torch.Tensor:
+    """x (S, n, D), y (R, n, D) float32, D in {2, 3, 5, 6} -> (S, R) float32: entry
+    [i, j] = the cost of the one-to-one match the auction finds between x[i] and
+    y[j] over all D components (ops.emd_auction, csrc/emd_auction.hip; no
+    assignment is written), divided by n: the units of pairwise_emd_nd.
+
+    ORIENTATION: the match is a bijection whose cost is at most
+    n * eps_rel * (the pair's largest squared distance) above the optimum's, and
+    the optimum does not depend on which cloud comes first.  Entries [i, j] of
+    pairwise_emd_auction(x, y) and [j, i] of pairwise_emd_auction(y, x) therefore
+    differ by at most eps_rel * (that largest squared distance), which is what
+    one_nna's joint matrix assumes.
+
+    Pairs are gathered in chunks; a chunk's gathered inputs (and, on the CPU, the
+    pair's cost matrices) stay under max_bytes.  The result does not depend on
+    the chunking: a pair's bits do not depend on the batch it is in.  An
+    unsupported or unequal D and unequal point counts raise ValueError; a pair
+    whose auction does not finish within max_rounds raises RuntimeError."""
+    if x.dim() != 3 or y.dim() != 3 or x.shape[2] != y.shape[2] \
+            or x.shape[2] not in ops.EMD_ND_DIMS:
+        raise ValueError(f"pairwise_emd_auction: expected (S, n, D) and (R, n, D), D in "
+                         f"{ops.EMD_ND_DIMS}, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError(f"pairwise_emd_auction: point counts differ ({x.shape[1]} and "
+                         f"{y.shape[1]})")
+    x, y = x.contiguous(), y.contiguous()
+    s, r, n, d = x.shape[0], y.shape[0], x.shape[1], x.shape[2]
+    out = torch.empty(s * r, dtype=torch.float32, device=x.device)
+    if s * r == 0 or n == 0:
+        return out.zero_().view(s, r)
+    # the gathered pair; the CPU backend also holds a pair's cost matrix three times
+    pair_bytes = 2 * n * d * 4 + (0 if x.is_cuda else 3 * n * n * 4)
+    if pair_bytes > max_bytes:
+        raise ValueError(f"pairwise_emd_auction: max_bytes = {max_bytes} is below one pair's "
+                         f"{pair_bytes} bytes")
+    chunk = min(max_bytes // pair_bytes, s * r, _EMD_MAX_PAIRS)
+    unfinished = 0
+    for p0 in range(0, s * r, chunk):
+        p = torch.arange(p0, min(p0 + chunk, s * r), device=x.device)
+        i, j = torch.div(p, r, rounding_mode="floor"), p % r
+        _, cost, rounds = ops.emd_auction(x[i], y[j], eps_rel=eps_rel, max_rounds=max_rounds,
+                                          want_assignment=False)
+        unfinished += int((rounds < 0).sum())
+        out[p0:p0 + p.numel()] = cost / n
+    if unfinished:
+        raise RuntimeError(f"pairwise_emd_auction: {unfinished} of {s * r} pairs did not finish "
+                           f"their auction within max_rounds = {max_rounds} rounds")
+    return out.view(s, r)
+
+
 def _argmin_first(m: torch.Tensor, dim: int) -> torch.Tensor:
     """argmin along dim, the LOWEST index among equal minima."""
     lo = m.min(dim=dim, keepdim=True).values
@@ -310,7 +367,7 @@ def jsd(sample: torch.Tensor, ref: torch.Tensor, resolution: int = 28) -> torch.
 @torch.no_grad()
 def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True,
                        n_points=None, jsd: bool = False, jsd_resolution: int = 28,
-                       emd_components: str = "xyz") -> dict:
+                       emd_components: str = "xyz", emd_match: str = "approx") -> dict:
     """sample (S, N, D), ref (R, M, D) float32 -> {mmd_cd, mmd_smp_cd, cov_cd,
     1nna_cd, 1nna_gen_cd, 1nna_ref_cd} and, with emd=True, the same six with
     _emd.  Chamfer runs over all D components (D in {2, 3, 5, 6}).  EMD needs
@@ -329,10 +386,22 @@ def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True
     density on purpose: a histogram of such a subsample measures the support of
     a shape, not where its points lie.  N and M may differ (the histograms are
     normalised); D = 2 raises ValueError.  With jsd=False the result is what it
-    was without the keyword."""
+    was without the keyword.
+
+    emd_match names the match behind the _emd keys: "approx", the approximate
+    match above, or "auction", the one-to-one match of pairwise_emd_auction (at its
+    default eps_rel and max_rounds) over the same components -- a symmetric
+    distance within a stated bound of the optimal bijection's, at most 2048 points
+    a cloud on HIP tensors (n_points brings larger clouds there).  Any other value
+    raises ValueError.  With "approx" the result is what it was without the
+    keyword."""
     if emd_components not in ("xyz", "all"):
         raise ValueError(f"generation_metrics: emd_components = {emd_components!r} is neither "
                          "'xyz' nor 'all'")
+    if emd_match not in ("approx", "auction"):
+        raise ValueError(f"generation_metrics: emd_match = {emd_match!r} is neither 'approx' "
+                         "nor 'auction'")
+    auction = emd_match == "auction"
     extra = {"jsd": _jsd(sample, ref, jsd_resolution)} if jsd else {}
     if n_points is not None:
         sample, ref = subsample(sample, n_points), subsample(ref, n_points)
@@ -348,12 +417,13 @@ def generation_metrics(sample: torch.Tensor, ref: torch.Tensor, emd: bool = True
 
     out = reduce(pairwise_chamfer, sample, ref, "cd")
     if emd and emd_components == "all":
-        out.update(reduce(pairwise_emd_nd, sample, ref, "emd"))
+        out.update(reduce(pairwise_emd_auction if auction else pairwise_emd_nd, sample, ref,
+                          "emd"))
     elif emd:
         if sample.shape[-1] < 3 or ref.shape[-1] < 3:
             raise ValueError("generation_metrics: EMD needs at least three components (xyz)")
-        out.update(reduce(pairwise_emd, sample[..., :3].contiguous(), ref[..., :3].contiguous(),
-                          "emd"))
+        out.update(reduce(pairwise_emd_auction if auction else pairwise_emd,
+                          sample[..., :3].contiguous(), ref[..., :3].contiguous(), "emd"))
     out.update(extra)
     return out
 

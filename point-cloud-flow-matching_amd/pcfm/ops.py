@@ -934,6 +934,53 @@ def matchcost_backward_nd(grad_cost: torch.Tensor, p1: torch.Tensor, p2: torch.T
     return [g1, g2]
 
 
+# --------------------------------------------------------------------------
+# assignment EMD by auction (include/pcfm_emd_auction.h, csrc/emd_auction.hip): a
+# one-to-one match within n * eps of the optimum.  No reference module has this
+# name; the contract is the header's.
+# --------------------------------------------------------------------------
+def emd_auction(p1: torch.Tensor, p2: torch.Tensor, eps_rel: float = 2.0 ** -16,
+                max_rounds: int = 1 << 20, want_assignment: bool = True):
+    """p1, p2 (B, n, D) float32, D in {2, 3, 5, 6} -> (assignment (B, n) int32 or
+    None, cost (B,) float32, rounds (B,) int32): assignment[b, i] is the point of
+    p2[b] matched to p1[b, i], a permutation whose cost -- the sum of the squared
+    distances of the matched points -- is at most n * eps_rel * (the largest
+    squared distance of the pair) above the optimum; rounds counts the bidding
+    rounds.  A pair that does not finish within max_rounds has rounds -1, an
+    assignment row of -1 and a NaN cost.  want_assignment=False skips writing the
+    assignment."""
+    host = _host(p1, p2)
+    for name, t in (("p1", p1), ("p2", p2)):
+        (_check_host if host else _check)(t, name, "f")
+    if p1.dim() != 3 or tuple(p1.shape) != tuple(p2.shape):
+        raise RuntimeError(f"emd_auction: expected two (B, n, D) tensors of one shape, got "
+                           f"{tuple(p1.shape)} and {tuple(p2.shape)}")
+    b, n, d = p1.shape
+    if d not in EMD_ND_DIMS:
+        raise RuntimeError(f"emd_auction: D = {d} is not one of {EMD_ND_DIMS}")
+    eps_rel, max_rounds = float(eps_rel), int(max_rounds)
+    if not 2.0 ** -20 <= eps_rel <= 0.5:     # a NaN fails both comparisons
+        raise RuntimeError(f"emd_auction: eps_rel = {eps_rel} outside [2^-20, 0.5]")
+    if not 1 <= max_rounds < 1 << 31:
+        raise RuntimeError(f"emd_auction: max_rounds = {max_rounds} outside [1, 2^31)")
+    if host:
+        assignment, cost, rounds = cpu_ops.emd_auction(p1, p2, eps_rel, max_rounds)
+        return (assignment if want_assignment else None), cost, rounds
+    top = _lib.query("pcfm_emd_auction_max_points", d)
+    if n > top:
+        raise RuntimeError(f"emd_auction: n = {n} above the {top} points the kernel holds "
+                           "(pcfm.metrics.subsample brings larger clouds there)")
+    assignment = torch.empty((b, n), dtype=torch.int32, device=p1.device) \
+        if want_assignment else None
+    cost = torch.empty((b,), dtype=torch.float32, device=p1.device)
+    rounds = torch.empty((b,), dtype=torch.int32, device=p1.device)
+    ws = _workspace(_lib.query("pcfm_emd_auction_workspace_bytes", b, n, d), p1)
+    _lib.call("pcfm_emd_auction_f32", _ptr(p1), _ptr(p2), b, n, d, eps_rel, max_rounds,
+              _ptr(assignment) if assignment is not None else None, _ptr(cost), _ptr(rounds),
+              _ptr(ws), ws.numel(), _stream(p1))
+    return assignment, cost, rounds
+
+
 def host_routed(ext, host, names):
     """A binding namespace that calls the torch C++ extension `ext` (HIP tensors
     only: csrc/torch_backend.cpp, torch_losses.cpp) and sends a call whose tensor
