@@ -518,6 +518,10 @@ int pcfm_head_silu_bwd(const void* da16, const float* uprev, const void* gprev, 
  * after it: SharedMLP's BN1d + ReLU (shared_mlp.py:15-27, slope = 0) and
  * PVConv's BN3d + LeakyReLU(0.1) (pvconv.py:20-30, slope = 0.1), over
  * x f32 [b][c][s] (s % 4 == 0).  torch.nn.functional.batch_norm semantics.
+ * Non-finite values propagate as through torch's modules: a NaN stays a NaN
+ * through either activation (ReLU is not max(t, 0)) and through the variance
+ * clamp, relu(-inf) = 0, and a dead ReLU unit passes no gradient, finite or not
+ * ("Non-finite values").
  * ---------------------------------------------------------------------- */
 
 size_t pcfm_bn_workspace_bytes(int b, int c, int s);

@@ -16,8 +16,25 @@ namespace pcfm {
 // one channel's constants
 struct BnChan {
   float m, is, g, bt, slope;
+  // A NaN argument stays NaN at either slope (F.relu, F.leaky_relu): the negative
+  // branch takes what compares <= 0, so a NaN is not selected into it.
   static __device__ __forceinline__ float act(float t, float slope) {
-    return t > 0.0f ? t : (slope == 0.0f ? 0.0f : t * slope);
+    return t <= 0.0f ? (slope == 0.0f ? 0.0f : t * slope) : t;
+  }
+  // whether the unit passes its gradient unscaled, as torch's backward decides it:
+  // ReLU's from its result (0 where that compares <= 0, so a NaN passes),
+  // LeakyReLU's from its argument (slope unless that compares > 0)
+  static __device__ __forceinline__ bool passes(float t, float slope) {
+    return slope == 0.0f ? !(t <= 0.0f) : t > 0.0f;
+  }
+  // d act / d t
+  static __device__ __forceinline__ float dact(float t, float slope) {
+    return passes(t, slope) ? 1.0f : slope;
+  }
+  // dz * dact(t); a dead ReLU unit gives 0 (torch's threshold backward), not
+  // dz * 0: a non-finite dz does not pass it
+  static __device__ __forceinline__ float gate(float t, float slope, float dz) {
+    return passes(t, slope) ? dz : (slope == 0.0f ? 0.0f : dz * slope);
   }
   __device__ __forceinline__ float xhat(float v) const { return (v - m) * is; }
   // the activation's argument bn(v)
@@ -28,7 +45,7 @@ struct BnChan {
   }
   // dz * act'(bn(v)): the gradient entering the BatchNorm
   __device__ __forceinline__ float grad(float v, float dz) const {
-    return pre(v) > 0.0f ? dz : dz * slope;
+    return gate(pre(v), slope, dz);
   }
   // the BatchNorm input's gradient, mg = sum grad / n and mgx = sum grad * xhat / n
   // over the channel

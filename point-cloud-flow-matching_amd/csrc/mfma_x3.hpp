@@ -16,9 +16,12 @@ namespace {
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// round-to-nearest-even fp32 -> bf16 bits (finite inputs)
+// round-to-nearest-even fp32 -> bf16 bits; a NaN stays a (quiet) NaN of its
+// sign -- the rounding add alone would carry a NaN of mantissa >= 0x7F8000 into
+// the sign bit, i.e. to -0.0
 __device__ __forceinline__ uint32_t bf16_bits(float x) {
   uint32_t u = __float_as_uint(x);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x0040u;
   u += 0x7FFFu + ((u >> 16) & 1u);
   return u >> 16;
 }

@@ -179,12 +179,14 @@ struct BnStat {
   float m, is, var;
   double n;  // values the statistics are over
 };
+// a variance's clamp at 0 that keeps a NaN (fmaxf returns its other operand)
+__device__ __forceinline__ float clamp_var(float v) { return v < 0.0f ? 0.0f : v; }
 // from s = sum (x - K), q = sum (x - K)^2 over n values (GroupNorm's groups too)
 __device__ __forceinline__ BnStat stat_of_shifted(float s, float q, double n, float K, float eps) {
   BnStat st;
   st.n = n;
   const float md = (float)(s / n);
-  st.var = fmaxf((float)(q / n) - md * md, 0.0f);
+  st.var = clamp_var((float)(q / n) - md * md);
   st.m = K + md;
   st.is = rsqrtf(st.var + eps);
   return st;
@@ -287,7 +289,7 @@ __global__ void __launch_bounds__(256)
     mu = wr[0][1];
     m2 = wr[0][2];
     for (int k = 1; k < 4; ++k) chan_merge(n, mu, m2, wr[k][0], wr[k][1], wr[k][2]);
-    const float var = fmaxf((float)(m2 / n), 0.0f);
+    const float var = clamp_var((float)(m2 / n));
     fin.publish(c, BnStat{(float)mu, rsqrtf(var + fin.eps), var, n}, mean, invstd);
   }
 }
@@ -689,9 +691,9 @@ __global__ void __launch_bounds__(256)
     for (int e = 0; e < 4; ++e) {
       const float xh = ch.xhat(xv[e]);
       const float t = ch.pre(xv[e]);
-      const float a = t > 0.0f ? 1.0f : ch.slope;
+      const float a = BnChan::dact(t, ch.slope);
       const float z = BnChan::act(t, ch.slope);
-      const float ag = a * dv[e];
+      const float ag = BnChan::gate(t, ch.slope, dv[e]);  // a * g at every finite g
       acc[0] = __builtin_fmaf(z, dv[e], acc[0]);
       acc[1] += ag;
       acc[2] += a;

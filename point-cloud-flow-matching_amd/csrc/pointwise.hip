@@ -235,7 +235,8 @@ __device__ __forceinline__ void group_stats(const f32x16 (&acc)[SI][NA], int i,
   const int m = mg + acc_row(r & 15, h);
   if (r < 16 && m < M) {
     const float a = v[0], mu_s = a / (float)nv;
-    stats[(size_t)m * P + gi] = make_float2(sr + mu_s, fmaxf(__builtin_fmaf(-a, mu_s, q), 0.0f));
+    const float m2 = __builtin_fmaf(-a, mu_s, q);  // clamped at 0; a NaN stays (fmaxf drops it)
+    stats[(size_t)m * P + gi] = make_float2(sr + mu_s, m2 < 0.0f ? 0.0f : m2);
   }
 }
 

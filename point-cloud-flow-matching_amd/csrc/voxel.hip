@@ -461,7 +461,8 @@ __global__ void __launch_bounds__(1024)
     const int bi = ec / h, j = ec - bi * h;
     float acc = 0.0f;
     for (int k = l16; k < c; k += 16) acc = __builtin_fmaf(ms[bi * c + k], w1s[j * c + k], acc);
-    const float v = fmaxf(se_group_sum(acc), 0.0f);
+    const float sum = se_group_sum(acc);
+    const float v = sum <= 0.0f ? 0.0f : sum;  // relu: a NaN stays (fmaxf would drop it)
     if (l16 == 0 && e < b * h) {
       hs[e] = v;
       hid[e] = v;
@@ -516,7 +517,8 @@ __global__ void __launch_bounds__(1024)
     float acc = 0.0f;
     for (int k = l16; k < c; k += 16) acc = __builtin_fmaf(dz2[bi * c + k], w2t[j * c + k], acc);
     acc = se_group_sum(acc);
-    if (l16 == 0 && e < b * h) dz1[e] = hs[e] > 0.0f ? acc : 0.0f;
+    // torch's relu backward: 0 where the result compares <= 0 (a NaN result passes)
+    if (l16 == 0 && e < b * h) dz1[e] = hs[e] <= 0.0f ? 0.0f : acc;
   }
   __syncthreads();
   for (int e = threadIdx.x; e < h * c; e += blockDim.x) {  // dW1 [h][c]: over b
