@@ -2,7 +2,7 @@
  * and its gradient) over D-component points (D = 2, 3, 5, 6), float32, for AMD
  * Instinct MI355X (gfx950).  A sibling of pcfm.h, pcfm_chamfer_nd.h,
  * pcfm_chamfer_cross.h, pcfm_fps.h and pcfm_occupancy.h, implemented by the same
- * libpcfm_hip.so (csrc/emd_nd.hip over csrc/emd_core.hpp) and under the same
+ * libpcfm_hip.so (csrc/emd.hip over csrc/emd_core.hpp) and under the same
  * conventions:
  *
  *   - every pointer is a device pointer, row-major contiguous, extents as stated;

@@ -12,7 +12,7 @@
 //     (csrc/Makefile NOPK).
 #pragma once
 
-#include <hip/hip_runtime.h>
+#include "pcfm_common.hpp"
 
 namespace pcfm {
 
@@ -24,22 +24,23 @@ constexpr int kPerBlock = kQ * kThreads;
 // are 2 * group_of(D) * D SGPRs, 48 at most
 constexpr int group_of(int d) { return d <= 3 ? 8 : 4; }
 
-// c, q: D components each.  ONE fixed fp32 chain (the build has
-// -ffp-contract=off):
+// c, q: D components each, float or double (the EMD's double entries).  ONE
+// fixed chain (the build has -ffp-contract=off):
 //   acc = d1*d1; acc = fma(d0, d0, acc); acc = fma(dk, dk, acc) for k = 2..D-1,
 //   dk = c[k] - q[k]
 // (c - q)^2 and (q - c)^2 have the same bits, so the direction does not matter.
-// At D = 3 that is sqdist3 (pcfm_common.hpp), the oracle's chain.
-template <int D>
-__device__ __forceinline__ float sqdist_nd(const float* c, const float* q) {
-  const float d1 = c[1] - q[1];
-  float acc = d1 * d1;
-  const float d0 = c[0] - q[0];
-  acc = __builtin_fmaf(d0, d0, acc);
+// At D = 3 that is sqdist3 (pcfm_common.hpp), the oracle's chain, in both types;
+// fmaT is its fused multiply-add by type.
+template <int D, typename T>
+__device__ __forceinline__ T sqdist_nd(const T* c, const T* q) {
+  const T d1 = c[1] - q[1];
+  T acc = d1 * d1;
+  const T d0 = c[0] - q[0];
+  acc = fmaT<T>(d0, d0, acc);
 #pragma unroll
   for (int k = 2; k < D; ++k) {
-    const float dk = c[k] - q[k];
-    acc = __builtin_fmaf(dk, dk, acc);
+    const T dk = c[k] - q[k];
+    acc = fmaT<T>(dk, dk, acc);
   }
   return acc;
 }

@@ -1,10 +1,9 @@
 // What the approximate EMD is, once: the level table, the arithmetic of a
 // level (exp, the three finalize expressions), the building blocks of the
 // kernels, the host plan of the workspace, the prologue of an entry and the
-// sequence of pass launches.  csrc/emd.hip (include/pcfm.h: three components,
-// float and double) and csrc/emd_nd.hip (include/pcfm_emd_nd.h: D = 2, 3, 5, 6
-// components, float) are both written over it, so that the two sets of entries
-// cannot drift apart: at D = 3 they return the same bits.
+// sequence of pass launches.  The kernels of csrc/emd.hip (include/pcfm.h: three
+// components, float and double; include/pcfm_emd_nd.h: D = 2, 3, 5, 6
+// components, float) are written over it.
 #pragma once
 
 #include "pcfm_common.hpp"
@@ -29,17 +28,6 @@ constexpr float level_log2e(int j) { return h_levels[j] * 1.4426950408889634f; }
 template <typename T>
 __device__ __forceinline__ T emd_exp2(T d2, T lvl2) {
   return (T)__builtin_amdgcn_exp2f((float)d2 * (float)lvl2);
-}
-
-template <typename T>
-__device__ __forceinline__ T fmaT(T a, T b, T c);
-template <>
-__device__ __forceinline__ float fmaT<float>(float a, float b, float c) {
-  return __builtin_fmaf(a, b, c);
-}
-template <>
-__device__ __forceinline__ double fmaT<double>(double a, double b, double c) {
-  return __builtin_fma(a, b, c);
 }
 
 constexpr int kEmdThreads = 256;  // the match, cost and gradient kernels' block

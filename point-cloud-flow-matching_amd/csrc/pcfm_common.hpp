@@ -67,6 +67,18 @@ __device__ __forceinline__ double sqdist3(double dx, double dy, double dz) {
   return __builtin_fma(dz, dz, __builtin_fma(dx, dx, dy * dy));
 }
 
+// The explicit fused multiply-add of a kernel templated on its scalar type.
+template <typename T>
+__device__ __forceinline__ T fmaT(T a, T b, T c);
+template <>
+__device__ __forceinline__ float fmaT<float>(float a, float b, float c) {
+  return __builtin_fmaf(a, b, c);
+}
+template <>
+__device__ __forceinline__ double fmaT<double>(double a, double b, double c) {
+  return __builtin_fma(a, b, c);
+}
+
 // A 1-D grid's block id dealt to the 8 XCDs in contiguous runs (T1 remap):
 // hardware sends block i to XCD i % 8; the id returned makes each XCD sweep one
 // contiguous eighth of [0, nwg), so concurrently resident blocks share rows in

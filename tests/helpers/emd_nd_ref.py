@@ -1,5 +1,5 @@
 """numpy fp64 reference of the approximate EMD over D-component points
-(include/pcfm_emd_nd.h, csrc/emd_nd.hip): emd_ref.approxmatch with pair_d2 taken
+(include/pcfm_emd_nd.h, csrc/emd.hip): emd_ref.approxmatch with pair_d2 taken
 over the D-component chain of sqdist_nd (csrc/chamfer_search.hpp),
 
     acc = d1*d1;  acc = fma(d0, d0, acc);  acc = fma(dk, dk, acc), k = 2 .. D-1,

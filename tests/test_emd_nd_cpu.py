@@ -1,5 +1,5 @@
 """CPU: the approximate EMD over D-component points (include/pcfm_emd_nd.h,
-csrc/emd_nd.hip) without a GPU -- the CPU backend against the float64 reference of
+csrc/emd.hip) without a GPU -- the CPU backend against the float64 reference of
 tests/helpers/emd_nd_ref.py and, at D = 3, against the existing functions bit for
 bit; the autograd wrapper; pairwise_emd_nd and the emd_components keyword of
 generation_metrics; the sixth ABI table, the host plan and the host-side
@@ -323,21 +323,30 @@ def test_plan_and_refusals_on_the_host():
 
 # ---- 6. the shipped device code ---------------------------------------------------------------------------
 def test_shipped_emd_nd_kernels_have_no_scratch(tmp_path):
+    """One kernel family <T, D> (row passes <T, D, PH>) serves the 3-D and the N-D
+    entries: float at D = 2, 3, 5, 6 and double at D = 3, every instance once."""
     assert codeobj.available(), "ROCm LLVM tools absent"
-    found = {}
+    names, found = [], {}
     for co in codeobj.extract(_lib.LIB_PATH, str(tmp_path)):
         for name, res in codeobj.kernel_resources(co).items():
-            if "emd_nd_" in name:
+            if "emd" in name and "emd_auction" not in name:
+                names.append(name)
                 found[name] = res
-    for kind, count in (("rowpass_kernelILi%dELi%dE", None), ("match_cost_kernelILi%dE", 1),
-                        ("cost_kernelILi%dE", 1), ("grad1_kernelILi%dE", 1),
-                        ("grad2_kernelILi%dE", 1), ("pack_kernelILi%dE", 1)):
-        for d in (2, 3, 5, 6):
-            pats = [kind % (d, ph) for ph in range(4)] if count is None else [kind % d]
+    assert len(names) == len(set(names)), sorted(names)      # no kernel in two code objects
+    insts = [("f", d) for d in (2, 3, 5, 6)] + [("d", 3)]
+    for kind, count in (("rowpass_kernelI%sLi%dELi%dEE", None), ("match_cost_kernelI%sLi%dEE", 1),
+                        ("cost_kernelI%sLi%dEE", 1), ("grad1_kernelI%sLi%dEE", 1),
+                        ("grad2_kernelI%sLi%dEE", 1), ("pack_kernelI%sLi%dEE", 1)):
+        for t, d in insts:
+            pats = [kind % (t, d, ph) for ph in range(4)] if count is None else [kind % (t, d)]
             for pat in pats:
-                assert sum("emd_nd_" + pat in k for k in found) == 1, pat
-    assert len(found) == 4 * (4 + 5) + 2, sorted(found)      # + cost_fin and grad1_fin
+                assert sum("emd_" + pat in k for k in found) == 1, pat
+    for t in "fd":                                           # cost_fin and grad1_fin: per T alone
+        for kind in ("cost_fin_kernelI%sE", "grad1_fin_kernelI%sE"):
+            assert sum("emd_" + kind % t in k for k in found) == 1, (kind, t)
+    # nothing else carries "emd": no second kernel for any <T, D, PH>
+    assert len(found) == 5 * (4 + 5) + 2 * 2, sorted(found)
     for k, res in found.items():
-        assert res["scratch"] == 0, (k, res)
+        assert res["scratch"] == 0, (k, res)                 # double too: the 3-D double kernels had none
         if "rowpass" in k:
             assert res["wg"] == 1024, (k, res)

@@ -1,4 +1,4 @@
-"""Digests of everything the EMD entries (csrc/emd.hip) return, from fixed seeds,
+"""Digests of everything the approximate-EMD entries (csrc/emd.hip) return, from fixed seeds,
 for a bit-for-bit comparison of two builds (dev tool):
 
     PCFM_LIB=<library> python tools/emd_parity.py out.json [tag]         # once per build (GPU)
@@ -8,7 +8,8 @@ for a bit-for-bit comparison of two builds (dev tool):
 
 One SHA-256 per returned tensor: approxmatch's match, matchcost's cost, the
 fused entry's match and cost, its cost-only cost, and matchcost_bwd's grad1 and
-grad2, for f32 and f64, at the shapes of tests/test_gpu_ops.py::
+grad2, for f32 and f64, and what the three pcfm_emd_nd.h entries return at
+D = 2, 5, 6 (clouds from the same seeds), at the shapes of tests/test_gpu_ops.py::
 test_emd_vs_fp64_reference plus (8, 2048, 2048), in the default form and under
 PCFM_EMD_FORM=unfused.
 
@@ -18,8 +19,9 @@ tests/helpers/emd_ref.py over those test shapes, under whatever PCFM_EMD_FORM is
 set (the bound of the test was measured this way on the retired split form).
 
 --host records pcfm_emd_workspace_bytes over b, n, m in {0, 1, 37, 64, 513,
-2048, 20000} and checks bytes(.., 8) == 2 * bytes(.., 4); the plan's own layout
-(regions end to end, packs aligned) is a static_assert in emd.hip."""
+2048, 20000} and checks bytes(.., 8) == 2 * bytes(.., 4), and
+pcfm_emd_nd_workspace_bytes over the same sizes at d = 2, 3, 5, 6; the plan's own
+layout (regions end to end, packs aligned) is a static_assert in emd_core.hpp."""
 import ctypes
 import hashlib
 import json
@@ -38,6 +40,7 @@ def host(out_path, tag="tree"):
     lib = ctypes.CDLL(os.environ.get("PCFM_LIB") or os.path.join(
         REPO, "point-cloud-flow-matching_amd", "csrc", "libpcfm_hip.so"))
     lib.pcfm_emd_workspace_bytes.restype = ctypes.c_size_t
+    lib.pcfm_emd_nd_workspace_bytes.restype = ctypes.c_size_t
     sizes = (0, 1, 37, 64, 513, 2048, 20000)
     val, bad = {}, []
     for b in sizes:
@@ -47,6 +50,9 @@ def host(out_path, tag="tree"):
                 val[f"workspace_bytes/{b}/{n}/{m}"] = w4
                 if w8 != 2 * w4:
                     bad.append((b, n, m))
+                for d in (2, 3, 5, 6):
+                    val[f"nd_workspace_bytes/{b}/{n}/{m}/{d}"] = int(
+                        lib.pcfm_emd_nd_workspace_bytes(b, n, m, d))
     with open(out_path, "w") as f:
         json.dump({"lib": tag, "digests": val, "f64_not_twice_f32": bad}, f)
     print(json.dumps({"values": len(val), "f64_not_twice_f32": bad}))
@@ -100,6 +106,18 @@ def main(out_path, tag="tree"):
                 put(f"{tag_}/fused", *ops.approxmatch_cost_forward(a, c))
                 put(f"{tag_}/cost_only", ops.approxmatch_cost_forward(a, c, want_match=False)[1])
                 put(f"{tag_}/grads", *ops.matchcost_backward(gc, a, c, match))
+                del match
+            for d in (2, 5, 6):   # the pcfm_emd_nd.h entries; D = 3 is the f32 kernels above
+                gen = torch.Generator(device="cuda").manual_seed(1000 * n + m + b)
+                a = torch.rand(b, n, d, device="cuda", generator=gen)
+                c = torch.rand(b, m, d, device="cuda", generator=gen)
+                gc = torch.rand(b, device="cuda", generator=gen)
+                tag_ = f"{form}/{b}x{n}x{m}/nd{d}"
+                match, cost = ops.approxmatch_cost_forward_nd(a, c)
+                put(f"{tag_}/fused", match, cost)
+                put(f"{tag_}/cost_only", ops.approxmatch_cost_forward_nd(a, c, want_match=False)[1])
+                put(f"{tag_}/cost", ops.matchcost_forward_nd(a, c, match))
+                put(f"{tag_}/grads", *ops.matchcost_backward_nd(gc, a, c, match))
                 del match
         os.environ.pop("PCFM_EMD_FORM", None)
     torch.cuda.synchronize()

@@ -1,6 +1,10 @@
 """EMD at the bench size (B=8, N=M=2048), default form: ms per call (events and
 host clock) of the forward with match kept, the cost-only forward and forward
-plus backward, one JSON line each.  Run under rocprofv3 --kernel-trace --stats
+plus backward, one JSON line each:
+
+    python tools/emd_probe.py [N [f32|f64]]
+
+Run under rocprofv3 --kernel-trace --stats
 for the per-kernel split; PCFM_LIB selects the library (A/B of two builds)."""
 import json
 import os
@@ -20,8 +24,10 @@ def main():
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev).manual_seed(0)
     b, n = 8, int(sys.argv[1]) if len(sys.argv) > 1 else 2048
-    p1 = torch.rand(b, n, 3, device=dev, generator=g)
-    p2 = torch.rand(b, n, 3, device=dev, generator=g)
+    dt = sys.argv[2] if len(sys.argv) > 2 else "f32"
+    dtype = {"f32": torch.float32, "f64": torch.float64}[dt]
+    p1 = torch.rand(b, n, 3, device=dev, generator=g, dtype=dtype)
+    p2 = torch.rand(b, n, 3, device=dev, generator=g, dtype=dtype)
     x = p1.detach().requires_grad_(True)  # the forward a backward follows: match kept
 
     def fwd_match():
@@ -50,7 +56,7 @@ def main():
         e1.record()
         torch.cuda.synchronize(dev)
         host = (time.perf_counter() - t0) * 1e3 / reps
-        print(json.dumps({"what": what, "b": b, "n": n, "ms_events": e0.elapsed_time(e1) / reps,
+        print(json.dumps({"what": what, "b": b, "n": n, "dtype": dt, "ms_events": e0.elapsed_time(e1) / reps,
                           "ms_host": host, "cost0": float(d.detach()[0])}), flush=True)
 
 
