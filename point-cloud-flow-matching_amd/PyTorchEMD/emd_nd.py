@@ -1,6 +1,6 @@
 """Approximate Earth Mover's Distance over D-component points, D in {2, 3, 5, 6}:
 PyTorchEMD/emd.py's autograd function over include/pcfm_emd_nd.h
-(csrc/emd_nd.hip), so that the EMD can see the colour of an xyz+rgb cloud and
+(csrc/emd.hip), so that the EMD can see the colour of an xyz+rgb cloud and
 serve as a loss on it.  Every component enters the squared distance with the same
 weight; scaling colour against position is the caller's data convention.
 

@@ -143,21 +143,6 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-
-__device__ __forceinline__ float rlf(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-
 // grid = (ceil(max(n,m) / (64 kCQ kCWaves)), 1, 2b).  s1/s2: sorted clouds,
 // box1/box2 their tile boxes, st1/st2 the sort's start[] (Morton cell -> first
 // sorted position).

@@ -16,31 +16,25 @@
 // ([64 rows][128 cols] bf16, 16-B chunks XOR-swizzled within a 256-B row) and
 // the MFMA operands (8 consecutive r per lane) come out of gfx950's
 // transposing LDS read ds_read_b64_tr_b16 (cdna_hip_programming.md T10).
+//
+// Shared with the other kernel families: the swizzled image and its transposed
+// read (swz256, tr_operand), zero_acc and acc_row come from mfma_x3.hpp, as in
+// conv3d.hip's conv3_wgrad_cl_kernel; the ordered reduce of the split partials
+// (ordered_sum4, also behind the column sums here, pointwise.hip's weight
+// gradient and head_film.hip's backward sums) and bf2f / f2bf from
+// pcfm_common.hpp.  Private: load_tile / store_tile (a bf16 source, no hi/lo
+// split) and the (value, index) maximum of rows_max, whose order is its own.
 #include <algorithm>
 #include <cstdlib>
 
+#include "mfma_x3.hpp"
 #include "pcfm_common.hpp"
 
 namespace pcfm {
 namespace {
 
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8h __attribute__((ext_vector_type(8)));
-typedef float f32x16h __attribute__((ext_vector_type(16)));
-
 constexpr int kRT = 64;    // rows (reduction) per K-step
 constexpr int kTile = 128; // output tile edge
-
-// byte offset of 16-B chunk `ch` (0..15) of LDS row `row` (256-B rows),
-// the T10 (b) swizzle: conflict-free ds_write_b128 rows and tr_b16 reads
-__device__ __forceinline__ int swz(int row, int ch) {
-  return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
-__device__ __forceinline__ v4s tr_read(const uint8_t* base, int off) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-      (__attribute__((address_space(3))) v4s*)(base + off));
-}
 
 // One 64-row x 128-col bf16 tile of a row-major matrix into 4 uint4 per thread
 // (rows >= R and columns >= ncols are zero).  MODE 2: ld % 8 == 0, 16-B
@@ -86,7 +80,7 @@ __device__ __forceinline__ void store_tile(uint8_t* img, int t, const uint4 (&v)
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int c = t + 256 * q;
-    *reinterpret_cast<uint4*>(img + swz(c >> 4, c & 15)) = v[q];
+    *reinterpret_cast<uint4*>(img + swz256(c >> 4, c & 15)) = v[q];
   }
 }
 
@@ -120,15 +114,9 @@ __global__ void __launch_bounds__(256) RW_WAVES
   const int t = threadIdx.x, lane = t & 63;
   const int w = __builtin_amdgcn_readfirstlane(t >> 6);
   const int wr = w >> 1, wc = w & 1;
-  const int g = lane >> 4, i16 = lane & 15, q4 = i16 >> 2, p4 = i16 & 3;
 
-  f32x16h acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.0f;
+  f32x16 acc[2][2];
+  zero_acc(acc);
 
   uint4 ra[4], rb[4];
   if (k0 < k1) {
@@ -145,24 +133,11 @@ __global__ void __launch_bounds__(256) RW_WAVES
     }
 #pragma unroll
     for (int kk = 0; kk < kRT / 16; ++kk) {
-      bf16x8h a[2], b[2];
-      const int row = kk * 16 + 8 * (g >> 1) + q4;
+      bf16x8 a[2], b[2];
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int col = wr * 64 + i * 32 + (g & 1) * 16 + 4 * p4;
-        const int off0 = swz(row, col >> 3) + 8 * (p4 & 1);
-        const int off1 = swz(row + 4, col >> 3) + 8 * (p4 & 1);
-        const v4s x0 = tr_read(imgA, off0), x1 = tr_read(imgA, off1);
-        a[i] = __builtin_bit_cast(bf16x8h, __builtin_shufflevector(x0, x1, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+      for (int i = 0; i < 2; ++i) a[i] = tr_operand(imgA, kk, wr * 64 + i * 32, lane);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = wc * 64 + j * 32 + (g & 1) * 16 + 4 * p4;
-        const int off0 = swz(row, col >> 3) + 8 * (p4 & 1);
-        const int off1 = swz(row + 4, col >> 3) + 8 * (p4 & 1);
-        const v4s y0 = tr_read(imgB, off0), y1 = tr_read(imgB, off1);
-        b[j] = __builtin_bit_cast(bf16x8h, __builtin_shufflevector(y0, y1, 0, 1, 2, 3, 4, 5, 6, 7));
-      }
+      for (int j = 0; j < 2; ++j) b[j] = tr_operand(imgB, kk, wc * 64 + j * 32, lane);
 #pragma unroll
       for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -184,7 +159,9 @@ __global__ void __launch_bounds__(256) RW_WAVES
     for (int j = 0; j < 2; ++j)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int m = m0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        // acc_row(e, h) with the lane half's 4 h added last: it then joins the
+        // row base once (written `+ acc_row(e, h)` the kernel gains 16 v_or_b32)
+        const int m = m0 + wr * 64 + i * 32 + acc_row(e, 0) + 4 * h;
         const int n = n0 + wc * 64 + j * 32 + r;
         if (m < M && n < N) pb[(size_t)m * N + n] = acc[i][j][e];
       }
@@ -194,28 +171,9 @@ __global__ void __launch_bounds__(256) RW_WAVES
 __global__ void __launch_bounds__(256)
     rows_wgrad_reduce_kernel(const float* __restrict__ part, size_t total, int S,
                              uint16_t* __restrict__ out) {
-  // 64 outputs per block, 4 thread groups over the splits, fixed combine order
-  __shared__ float red[4][64];
-  const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const size_t i = (size_t)blockIdx.x * 64 + cl;
-  float sum = 0.0f;
-  if (i < total) {
-    int q = grp;
-    // 4 of the group's partials loaded before they are added (same order)
-    for (; q + 12 < S; q += 16) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = part[(size_t)(q + 4 * u) * total + i];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) sum = sum + v[u];
-    }
-    for (; q < S; q += 4) sum = sum + part[(size_t)q * total + i];
-  }
-  red[grp][cl] = sum;
-  __syncthreads();
-  if (grp == 0 && i < total)
-    out[i] = __builtin_bit_cast(
-        uint16_t, (__bf16)(((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl]));
+  const size_t i = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const float sum = ordered_sum4(part + i, total, S, i < total);
+  if (threadIdx.x < 64 && i < total) out[i] = (uint16_t)f2bf(sum);
 }
 
 // blocks per CU the split count aims at (dev knob PCFM_RW_BPC, measurement)
@@ -328,7 +286,7 @@ __global__ void __launch_bounds__(256)
     if (c < C) {
       for (int r = n0 + wave; r < n1; r += 4) {
         const uint32_t u = *reinterpret_cast<const uint32_t*>(h + ((size_t)b * N + r) * C + c);
-        const float v0 = __uint_as_float(u << 16), v1 = __uint_as_float(u & 0xFFFF0000u);
+        const float v0 = bf2f(u), v1 = bf2f(u >> 16);
         if (max_better(v0, r, m0, i0)) { m0 = v0; i0 = r; }
         if (max_better(v1, r, m1, i1)) { m1 = v1; i1 = r; }
       }
@@ -365,6 +323,8 @@ __global__ void __launch_bounds__(256)
     const int i = pi[((size_t)b * P + p) * C + c];
     if (max_better(v, i, m, mi)) { m = v; mi = i; }
   }
+  // m is a widened bf16: its high half is the value, exactly (no rounding cast,
+  // which could also change a NaN's bits)
   val[(size_t)b * C + c] = (uint16_t)(__float_as_uint(m) >> 16);
   idx[(size_t)b * C + c] = mi;
 }
@@ -400,7 +360,7 @@ __global__ void __launch_bounds__(256)
     if constexpr (BF16) {
       const uint32_t q = *reinterpret_cast<const uint32_t*>(
           reinterpret_cast<const uint16_t*>(x) + o);
-      return make_float2(__uint_as_float(q << 16), __uint_as_float(q & 0xFFFF0000u));
+      return make_float2(bf2f(q), bf2f(q >> 16));
     } else {
       return *reinterpret_cast<const float2*>(reinterpret_cast<const float*>(x) + o);
     }
@@ -440,28 +400,12 @@ __global__ void __launch_bounds__(256)
   }
 }
 
-// grid (ceil(C / 64), B): 4 thread groups take every 4th partial, combined in order
+// grid (ceil(C / 64), B): the ordered sum of batch b's P partials per column
 __global__ void __launch_bounds__(256)
     colsum_final_kernel(const float* __restrict__ part, int P, int C, float* __restrict__ out) {
-  __shared__ float red[4][64];
-  const int b = blockIdx.y, cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl;
-  float s = 0.0f;
-  if (c < C) {
-    int p = grp;
-    // 4 of the group's partials loaded before they are added (same order)
-    for (; p + 12 < P; p += 16) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = part[((size_t)b * P + p + 4 * u) * C + c];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s += v[u];
-    }
-    for (; p < P; p += 4) s += part[((size_t)b * P + p) * C + c];
-  }
-  red[grp][cl] = s;
-  __syncthreads();
-  if (grp == 0 && c < C) out[(size_t)b * C + c] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+  const int b = blockIdx.y, c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const float s = ordered_sum4(part + (size_t)b * P * C + c, C, P, c < C);
+  if (threadIdx.x < 64 && c < C) out[(size_t)b * C + c] = s;
 }
 
 // ContextNet's t-gate blend (models.py:533-541) fused with the (B, C, N) ->

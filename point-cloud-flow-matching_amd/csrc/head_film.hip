@@ -29,6 +29,11 @@
 // residual sum recomputed instead of stored.  h_1 may carry a per-batch fp32
 // bias row hb[b] (the input Linear's columns that see the batch-constant
 // embedding, folded out of the GEMM): h_1 = bf16(h16 + hb[b]).
+//
+// Shared (pcfm_common.hpp): wave_sum, bf2f / f2bf, and stage 1 of the reduce,
+// ordered_sum4 -- the order head.hip's and pointwise.hip's split gradients use.
+// Private: the row loads / stores (a wave per row), the per-block combine over
+// the four waves and film_bwd_reduce2 (a plain sum over the batch).
 #include <algorithm>
 
 #include "pcfm_common.hpp"
@@ -47,17 +52,6 @@ namespace {
 #endif
 constexpr int kRowsPerBlock = 256;  // 4 waves x 64 rows, one batch element
 constexpr int kSums = 5;            // d sp1, d shift, d gamma, d beta, d bias_prev
-
-__device__ __forceinline__ float bf2f(uint32_t b) { return __uint_as_float(b << 16); }
-__device__ __forceinline__ uint32_t f2bf(float x) {
-  return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)x);
-}
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
 
 template <int NV>
 __device__ __forceinline__ void ld_f32(const float* __restrict__ p, int lane, float (&v)[NV][4]) {
@@ -327,35 +321,18 @@ __global__ void __launch_bounds__(256) FILM_BWD_ATTR
   }
 }
 
-// Stage 1: per-batch sums of the block partials, chunk order fixed (4 thread
-// groups take every 4th chunk, combined in group order).  k = 0, 1 go straight
+// Stage 1: per-batch sums of the block partials in the fixed chunk order of
+// ordered_sum4 (pcfm_common.hpp).  k = 0, 1 go straight
 // to dsp1 / dshift [B][W]; k = 2..4 go to perb[k - 2][B][W] for stage 2.
 // grid = (ceil(W / 64), 5, B), 256 threads.
 __global__ void __launch_bounds__(256)
     film_bwd_reduce_kernel(const float* __restrict__ part, int B, int chunks, int W,
                            float* __restrict__ dsp1, float* __restrict__ dshift,
                            float* __restrict__ perb) {
-  __shared__ float red[4][64];
-  const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + cl, k = blockIdx.y, b = blockIdx.z;
-  float s = 0.0f;
-  if (c < W) {
-    const float* p = part + ((size_t)b * chunks * kSums + k) * W + c;
-    int q = grp;
-    // 4 of the group's partials loaded before they are added (same order)
-    for (; q + 12 < chunks; q += 16) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = p[(size_t)(q + 4 * u) * kSums * W];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s += v[u];
-    }
-    for (; q < chunks; q += 4) s += p[(size_t)q * kSums * W];
-  }
-  red[grp][cl] = s;
-  __syncthreads();
-  if (grp != 0 || c >= W) return;
-  s = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63), k = blockIdx.y, b = blockIdx.z;
+  const float s = ordered_sum4(part + ((size_t)b * chunks * kSums + k) * W + c, (size_t)kSums * W,
+                               chunks, c < W);
+  if (threadIdx.x >= 64 || c >= W) return;
   float* out = k == 0 ? dsp1 : k == 1 ? dshift : perb + (size_t)(k - 2) * B * W;
   if (out != nullptr) out[(size_t)b * W + c] = s;
 }

@@ -1,5 +1,9 @@
 // bf16x3 matrix-core machinery shared by the voxel convolution (conv3d.hip)
-// and the pointwise (1x1) convolution (pointwise.hip).
+// and the pointwise (1x1) convolution (pointwise.hip).  The pieces that do not
+// depend on the hi/lo split -- zero_acc, acc_row and the transposed-read image
+// (swz256, tr_read16, tr_operand) -- also serve the per-point head's plain-bf16
+// weight gradient (head.hip's rows_wgrad_kernel), beside conv3d.hip's
+// conv3_wgrad_cl_kernel.
 //
 // Every fp32 operand x is split into hi = bf16(x) and lo = bf16(x - hi);
 // a*b ~= ah*bh + ah*bl + al*bh with fp32 accumulation in the MFMA (the al*bl

@@ -79,6 +79,70 @@ __device__ __forceinline__ double fmaT<double>(double a, double b, double c) {
   return __builtin_fma(a, b, c);
 }
 
+// Wave-wide (64 lanes) butterfly reductions.  wave_sum leaves the sum in every
+// lane; wave_max / wave_min return it wave-uniform (one scalar register).
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+// lane l's value of v, wave-uniform (v_readlane; l uniform)
+__device__ __forceinline__ float rlf(float v, int l) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
+}
+
+// bf16 bits (low 16 of b; the higher bits are shifted out) widened to fp32, and
+// fp32 rounded to bf16 bits by the compiler's cast (v_cvt_pk_bf16_f32, nearest
+// even).  mfma_x3.hpp's bf16_bits is the same rounding in integer arithmetic
+// with the NaN result pinned to (bits >> 16) | 0x40; the cast leaves a NaN's
+// bits to the hardware, so the two are not interchangeable where a NaN's bits
+// are part of a pinned result.
+__device__ __forceinline__ float bf2f(uint32_t b) { return __uint_as_float(b << 16); }
+__device__ __forceinline__ uint32_t f2bf(float x) {
+  return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)x);
+}
+
+// The ordered sum of S partials -- the determinism contract of the split
+// gradients (pointwise and head weight gradients, column sums, FiLM backward
+// sums).  A 256-thread block owns 64 outputs: thread t serves output t % 64 in
+// group g = t / 64, and p points at partial 0 of that output, partial q lying
+// at p[q * stride].  A thread past the last output passes live = false: it
+// reads nothing and still joins the barrier.  Group g adds partials g, g + 4,
+// ... in that order, 4 of them loaded before they are added while q + 12 < S (a
+// thread otherwise chains S / 4 dependent loads), and the groups combine as
+// ((r0 + r1) + r2) + r3.  Every thread returns the sum; one call per kernel
+// (the barrier is block-wide).
+__device__ __forceinline__ float ordered_sum4(const float* __restrict__ p, size_t stride, int S,
+                                              bool live) {
+  __shared__ float red[4][64];
+  const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
+  float sum = 0.0f;
+  if (live) {
+    int q = grp;
+    for (; q + 12 < S; q += 16) {
+      float v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = p[(size_t)(q + 4 * u) * stride];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) sum = sum + v[u];
+    }
+    for (; q < S; q += 4) sum = sum + p[(size_t)q * stride];
+  }
+  red[grp][cl] = sum;
+  __syncthreads();
+  return ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+}
+
 // A 1-D grid's block id dealt to the 8 XCDs in contiguous runs (T1 remap):
 // hardware sends block i to XCD i % 8; the id returned makes each XCD sweep one
 // contiguous eighth of [0, nwg), so concurrently resident blocks share rows in

@@ -749,27 +749,10 @@ __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))
 __global__ void __launch_bounds__(256)
     pw_wgrad_reduce_kernel(const float* __restrict__ part, size_t total, int S,
                            float* __restrict__ dw) {
-  // 64 outputs per block; 4 thread groups take every 4th split, combined in
-  // group order (deterministic), so a thread chains S / 4 dependent adds
-  __shared__ float red[4][64];
-  const int cl = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const size_t i = (size_t)blockIdx.x * 64 + cl;
-  float sum = 0.0f;
-  if (i < total) {
-    int q = grp;
-    // 4 of the group's partials loaded before they are added (same order)
-    for (; q + 12 < S; q += 16) {
-      float v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = part[(size_t)(q + 4 * u) * total + i];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) sum = sum + v[u];
-    }
-    for (; q < S; q += 4) sum = sum + part[(size_t)q * total + i];
-  }
-  red[grp][cl] = sum;
-  __syncthreads();
-  if (grp == 0 && i < total) dw[i] = ((red[0][cl] + red[1][cl]) + red[2][cl]) + red[3][cl];
+  // 64 outputs per block, the splits added in ordered_sum4's order (deterministic)
+  const size_t i = (size_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const float sum = ordered_sum4(part + i, total, S, i < total);
+  if (threadIdx.x < 64 && i < total) dw[i] = sum;
 }
 
 // The weight gradient's kernel, grid and workspace for a shape: ONE decision,

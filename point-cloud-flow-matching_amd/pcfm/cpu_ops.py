@@ -465,7 +465,7 @@ def matchcost_backward(grad_cost: torch.Tensor, xyz1: torch.Tensor, xyz2: torch.
     return [g1, g2]
 
 
-# the same three over D-component points (include/pcfm_emd_nd.h, csrc/emd_nd.hip):
+# the same three over D-component points (include/pcfm_emd_nd.h, csrc/emd.hip):
 # every component enters the squared distance with the same weight
 def approxmatch_forward_nd(p1: torch.Tensor, p2: torch.Tensor) -> torch.Tensor:
     """approxmatch over p1 (b, n, D), p2 (b, m, D), D >= 2 -> match (b, m, n); at

@@ -12,7 +12,7 @@ Each of the first three reduces an (S, R) matrix of cloud-to-cloud distances:
   * pairwise_emd -- the approximate-match cost of PyTorchEMD over gathered
     chunks of pairs (ops.approxmatch_cost_forward, no match matrix written);
   * pairwise_emd_nd -- the same over all D components of the points
-    (ops.approxmatch_cost_forward_nd, csrc/emd_nd.hip), so that the EMD figures
+    (ops.approxmatch_cost_forward_nd, csrc/emd.hip), so that the EMD figures
     see the colour of xyz+rgb clouds;
   * pairwise_emd_auction -- the cost of a one-to-one match within a stated bound
     of the optimal bijection's (ops.emd_auction, csrc/emd_auction.hip), over all D

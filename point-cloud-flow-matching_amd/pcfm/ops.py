@@ -858,7 +858,7 @@ emd_cuda = types.SimpleNamespace(approxmatch_forward=approxmatch_forward,
 
 # --------------------------------------------------------------------------
 # the same over D-component points, D in {2, 3, 5, 6}, float32
-# (include/pcfm_emd_nd.h, csrc/emd_nd.hip); every component has the same weight
+# (include/pcfm_emd_nd.h, csrc/emd.hip); every component has the same weight
 # --------------------------------------------------------------------------
 EMD_ND_DIMS = (2, 3, 5, 6)
 

@@ -1,5 +1,5 @@
 """GPU: the approximate EMD over D-component points (include/pcfm_emd_nd.h,
-csrc/emd_nd.hip) -- against the float64 reference of tests/helpers/emd_nd_ref.py,
+csrc/emd.hip) -- against the float64 reference of tests/helpers/emd_nd_ref.py,
 against the 3-D kernels bit for bit, the gradients against the float64 closed
 form, the contract (two runs, a side stream, the batch, degenerate sizes, the
 refusals, guarded and stale memory), the fused PH 3 against the unfused passes,

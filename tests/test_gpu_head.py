@@ -39,6 +39,32 @@ def test_rows_wgrad_vs_fp64(ops, rows, m, n):
     _check_bf16_sum(out, a.double().t() @ b.double())
 
 
+# Partial counts at the loop edges of the ordered reduce (ordered_sum4 in
+# csrc/pcfm_common.hpp): group g of 4 adds partials g, g + 4, ..., four loaded at
+# a time while q + 12 < S, then a stride-4 tail.  1: three groups idle; 3, 4, 5:
+# the tail alone, up to the first group with two partials; 12, 13: the batched
+# loop entered by no group / by group 0 only; 16, 17: by every group, with no
+# tail / a tail in group 0; 29: a second batch in group 0 beside three-partial
+# tails in the others; 33: two batches in every group and a tail in group 0.
+REDUCE_S = (1, 3, 4, 5, 12, 13, 16, 17, 29, 33)
+
+
+@pytest.mark.parametrize("s", REDUCE_S)
+def test_rows_wgrad_reduce_loop_edges(ops, s):
+    """One 128 x 128 tile over 512 s rows: the split plan gives steps / 8 = s
+    partials (asserted on the workspace, so a changed plan cannot hollow this out)."""
+    from pcfm import _lib
+    m = n = 128
+    rows = 512 * s
+    assert _lib.query("pcfm_rows_wgrad_workspace_bytes", rows, m, n) == s * m * n * 4
+    g = torch.Generator(device="cuda").manual_seed(100 + s)
+    a = torch.randn(rows, m, device="cuda", generator=g).bfloat16()
+    b = torch.randn(rows, n, device="cuda", generator=g).bfloat16()
+    out = ops.rows_wgrad_bf16(a, b)
+    _check_bf16_sum(out, a.double().t() @ b.double())
+    assert torch.equal(ops.rows_wgrad_bf16(a, b), out)
+
+
 def test_rows_wgrad_strided_rows(ops):
     """A column slice of a wider tensor (row stride > width), as autograd can hand in."""
     g = torch.Generator(device="cuda").manual_seed(5)
@@ -269,6 +295,24 @@ def test_rows_colsum_matches_sum(ops, shape, dtype):
     assert got.shape == want.shape and got.dtype == torch.float32
     assert ((got.double() - want).abs().max() / scale).item() < 1e-6
     assert torch.equal(ops.rows_colsum(x), got)  # deterministic
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32], ids=["bf16", "fp32"])
+@pytest.mark.parametrize("s", REDUCE_S)
+def test_rows_colsum_reduce_loop_edges(ops, s, dtype):
+    """(1, 256 s, 64): the stage-1 plan gives s partials per column (asserted on
+    the workspace); same reference and bound as test_rows_colsum_matches_sum."""
+    from pcfm import _lib
+    rows, c = 256 * s, 64
+    assert _lib.query("pcfm_rows_colsum_workspace_bytes", 1, rows, c) == s * c * 4
+    g = torch.Generator(device="cuda").manual_seed(200 + s)
+    x = torch.randn(1, rows, c, device="cuda", generator=g).to(dtype)
+    got = ops.rows_colsum(x)
+    want = x.double().sum(dim=-2)
+    scale = x.double().abs().sum(dim=-2).max()
+    assert got.shape == want.shape and got.dtype == torch.float32
+    assert ((got.double() - want).abs().max() / scale).item() < 1e-6
+    assert torch.equal(ops.rows_colsum(x), got)
 
 
 def test_tgate_matches_torch(ops):

@@ -50,7 +50,8 @@ emulation by test_head_film_ref_cpu.py::test_checks_reject_one_line_mutations:
   per batch element, so u of every row of b > 0 is wrong at O(0.1) ->
   test_film_forward fails on u at every shape with b > 1; the same index in the
   backward's constant load fails test_film_backward (dh, dgamma, dbeta) there.
-* start the reduce's tail loop at `q + 4`: every reduce group drops its first
+* start the reduce's tail loop (now ordered_sum4's, in pcfm_common.hpp, shared
+  with head.hip and pointwise.hip) at `q + 4`: every reduce group drops its first
   tail partial; group 0's is chunk 0 whenever chunks < 13, so all column sums of
   test_film_backward and test_silu_pair fail from one chunk up, and at 13 and 18
   chunks one to four partials are missing.
@@ -143,6 +144,34 @@ def test_film_backward(case, report):
     if inp["first"]:
         assert out["dbias_b"].shape == (b, w)
     R.check_film_backward(out, ref, inp["n"], lambda name, v: rec(report, name, v))
+
+
+@pytest.mark.parametrize("s", [1, 3, 4, 5, 12, 13, 16, 17, 29, 33])
+def test_film_backward_reduce_loop_edges(ops, s):
+    """b = 1, w = 256, n = 256 s: s chunks (asserted on the workspace), the chunk
+    counts at the loop edges of the ordered reduce (ordered_sum4 in
+    csrc/pcfm_common.hpp: four partials loaded at a time while q + 12 < s, then a
+    stride-4 tail, in each of 4 groups) between and beyond SHAPES' 1, 2, 13 and
+    18.  The first-block form, which returns every sum (dbias_b too), through
+    test_film_backward's checks and bounds; two calls return equal bits."""
+    from pcfm import _lib
+    b, w, n = 1, 256, 256 * s
+    assert _lib.query("pcfm_head_bwd_workspace_bytes", b, n, w) == (b * s * 5 + 3 * b) * w * 4
+    inp = R.make_inputs(b, n, w, True)
+    ref = R.film_ref(inp)
+    u, _, mean, rstd = _fwd(ops, inp)
+
+    def bwd():
+        res = ops.head_film_bwd(_dev(inp["dh_next"]), _dev(inp["da16"]), u, _dev(inp["h16"]), None,
+                                None, mean, rstd, _dev(inp["gamma"]), _dev(inp["beta"]),
+                                _dev(inp["sp1"]), n, want_dh=True, hbias=_dev(inp["hbias"]))
+        return [t.cpu() for t in res]
+    r0, r1 = bwd(), bwd()
+    names = ("dh", "dh16", "dsp1", "dshift", "dgamma", "dbeta", "dbias", "dbias_b")
+    assert len(r0) == len(names)
+    for x0, x1 in zip(r0, r1):
+        assert torch.equal(x0, x1)
+    R.check_film_backward(dict(zip(names, r0)), ref, n, lambda name, v: None)
 
 
 @pytest.mark.parametrize("shape", R.SHAPES, ids=[R.shape_id(s) for s in R.SHAPES])
