@@ -2,67 +2,10 @@
 third_party/ChamferDistancePytorch/chamfer6D/dist_chamfer_6D.py): nearest
 neighbours over 6-component points, e.g. xyz + rgb clouds (callers scale the
 colour channels themselves, as with the reference's module).
-
-Shaped as chamfer3D/dist_chamfer_3D.py: `chamfer_6D` is the native module
-(forward/backward write caller-allocated tensors and return 1 on success, 0
-after printing the error); the autograd Function allocates its outputs on the
-device.  By default `chamfer_6D` is the ctypes binding (pcfm.ops.chamfer_6D over
-include/pcfm_chamfer_nd.h, which also runs CPU tensors); PCFM_TORCH_BACKEND=1
-selects the torch C++ extension `chamfer6D/chamfer_6D*.so`
-(csrc/torch_losses.cpp) for HIP tensors, CPU tensors still going to the ctypes
-binding's CPU backend.
+Built by pcfm/chamfer_dist.py, which says what each name is.
 """
-import os
-
-import torch
-from torch import nn
-from torch.autograd import Function
-
-from pcfm.ops import chamfer_6D
-
-if os.environ.get("PCFM_TORCH_BACKEND") == "1":
-    from chamfer6D import chamfer_6D as _ext  # the torch-extension module
-    from pcfm.ops import host_routed
-    chamfer_6D = host_routed(_ext, chamfer_6D, ["forward", "backward"])
+from pcfm.chamfer_dist import make
 
 __all__ = ["chamfer_6D", "chamfer_6DFunction", "chamfer_6DDist"]
 
-
-def _outputs(xyz1, xyz2):
-    b, n, d1 = xyz1.shape
-    _, m, d2 = xyz2.shape
-    assert d1 == 6 and d2 == 6, \
-        "Wrong last dimension for the chamfer distance 's input! Check with .size()"
-    dev = xyz1.device
-    return (torch.empty(b, n, device=dev), torch.empty(b, m, device=dev),
-            torch.empty(b, n, dtype=torch.int32, device=dev),
-            torch.empty(b, m, dtype=torch.int32, device=dev))
-
-
-class chamfer_6DFunction(Function):
-    @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
-    def forward(ctx, xyz1, xyz2):
-        dist1, dist2, idx1, idx2 = _outputs(xyz1, xyz2)
-        if not chamfer_6D.forward(xyz1, xyz2, dist1, dist2, idx1, idx2):
-            raise RuntimeError("chamfer_6D.forward failed")
-        ctx.save_for_backward(xyz1, xyz2, idx1, idx2)
-        ctx.mark_non_differentiable(idx1, idx2)
-        return dist1, dist2, idx1, idx2
-
-    @staticmethod
-    @torch.amp.custom_bwd(device_type="cuda")
-    def backward(ctx, graddist1, graddist2, gradidx1, gradidx2):
-        xyz1, xyz2, idx1, idx2 = ctx.saved_tensors
-        g1 = torch.zeros_like(xyz1)
-        g2 = torch.zeros_like(xyz2)
-        ok = chamfer_6D.backward(xyz1, xyz2, g1, g2, graddist1.contiguous(),
-                                 graddist2.contiguous(), idx1, idx2)
-        if not ok:
-            raise RuntimeError("chamfer_6D.backward failed")
-        return g1, g2
-
-
-class chamfer_6DDist(nn.Module):
-    def forward(self, input1, input2):
-        return chamfer_6DFunction.apply(input1.contiguous(), input2.contiguous())
+chamfer_6D, _, chamfer_6DFunction, chamfer_6DDist = make(6)

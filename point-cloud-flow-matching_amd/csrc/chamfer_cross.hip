@@ -86,6 +86,8 @@ __global__ void __launch_bounds__(kThreads)
       const int j = qbase + q * kThreads + threadIdx.x;
       acc += j < nq ? (double)best[q] : 0.0;
     }
+    // wave_add written out: through the call the kernel is scheduled differently
+    // ("What the point-cloud kernels share")
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) acc += __shfl_xor(acc, off, 64);
     // two slots, alternating: thread 0 reads slot (pc & 1) before it arrives at
@@ -148,9 +150,7 @@ using namespace pcfm;
 
 extern "C" int pcfm_chamfer_cross_abi_version(void) { return PCFM_CHAMFER_CROSS_ABI_VERSION; }
 
-extern "C" int pcfm_chamfer_cross_supported(int d) {
-  return d == 2 || d == 3 || d == 5 || d == 6;
-}
+extern "C" int pcfm_chamfer_cross_supported(int d) { return point_dim_ok(d); }
 
 extern "C" size_t pcfm_chamfer_cross_workspace_bytes(int s, int r, int n, int m, int d) {
   if (s <= 0 || r <= 0 || n <= 0 || m <= 0 || !pcfm_chamfer_cross_supported(d) ||
@@ -190,12 +190,9 @@ extern "C" int pcfm_chamfer_cross_fwd(const float* a, const float* b, int s, int
   double* part0 = (double*)ws;
   double* part1 = part0 + (qb0 > 1 ? pairs * qb0 : 0);
   const int items0 = s * t0 * qb0, items1 = r * t1 * qb1;  // <= s * r * (qb0 + qb1) < 2^31
-  switch (d) {
-    case 2: launch<2>(a, b, s, r, n, m, kt, items0, items1, ab, ba, part0, part1, st); break;
-    case 3: launch<3>(a, b, s, r, n, m, kt, items0, items1, ab, ba, part0, part1, st); break;
-    case 5: launch<5>(a, b, s, r, n, m, kt, items0, items1, ab, ba, part0, part1, st); break;
-    default: launch<6>(a, b, s, r, n, m, kt, items0, items1, ab, ba, part0, part1, st); break;
-  }
+  with_dim(d, [&](auto dc) {
+    launch<decltype(dc)::value>(a, b, s, r, n, m, kt, items0, items1, ab, ba, part0, part1, st);
+  });
   const dim3 fin(ceil_div((long long)pairs, 256));
   if (qb0 > 1)
     hipLaunchKernelGGL(cross_finalize_kernel, fin, dim3(256), 0, st, (const double*)part0, pairs,

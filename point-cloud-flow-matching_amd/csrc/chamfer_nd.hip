@@ -108,7 +108,8 @@ __global__ void __launch_bounds__(kThreads)
       dist[o] = best[q];
       idx[o] = bi[q];
     } else {
-      atomicMin(key + o, pack_key(best[q], bi[q]));
+      // d >= 0: the smaller distance, then the lower index, whatever the arrival order
+      atomicMin(key + o, min_key(__float_as_uint(best[q]), bi[q]));
     }
   }
 }
@@ -123,8 +124,8 @@ __global__ void key_unpack_kernel(const unsigned long long* __restrict__ key, si
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < total) {
     const unsigned long long k = key[i];
-    dist[i] = __uint_as_float((unsigned)(k >> 32));
-    idx[i] = (int)(unsigned)(k & 0xffffffffu);
+    dist[i] = __uint_as_float(key_hi(k));
+    idx[i] = min_key_index(k);
   }
 }
 
@@ -232,12 +233,10 @@ int brute_fwd(const char* what, const float* p1, const float* p2, int b, int n, 
     hipLaunchKernelGGL(key_init_kernel, dim3(ceil_div((long long)total, 256)), dim3(256), 0, st,
                        key1, total);
   }
-  switch (d) {
-    case 2: launch_fwd<2>(p1, p2, b, n, m, splits, dist1, dist2, idx1, idx2, key1, key2, st); break;
-    case 3: launch_fwd<3>(p1, p2, b, n, m, splits, dist1, dist2, idx1, idx2, key1, key2, st); break;
-    case 5: launch_fwd<5>(p1, p2, b, n, m, splits, dist1, dist2, idx1, idx2, key1, key2, st); break;
-    default: launch_fwd<6>(p1, p2, b, n, m, splits, dist1, dist2, idx1, idx2, key1, key2, st); break;
-  }
+  with_dim(d, [&](auto dc) {
+    launch_fwd<decltype(dc)::value>(p1, p2, b, n, m, splits, dist1, dist2, idx1, idx2, key1, key2,
+                                    st);
+  });
   if (splits > 1) {
     const size_t t1 = (size_t)b * n, t2 = (size_t)b * m;
     hipLaunchKernelGGL(key_unpack_kernel, dim3(ceil_div((long long)t1, 256)), dim3(256), 0, st,
@@ -252,12 +251,9 @@ int brute_bwd(const char* what, const float* p1, const float* p2, int b, int n, 
               const float* gd1, const float* gd2, const int* idx1, const int* idx2, float* g1,
               float* g2, hipStream_t st) {
   if (b == 0 || n == 0 || m == 0) return PCFM_OK;
-  switch (d) {
-    case 2: launch_bwd<2>(p1, p2, b, n, m, gd1, gd2, idx1, idx2, g1, g2, st); break;
-    case 3: launch_bwd<3>(p1, p2, b, n, m, gd1, gd2, idx1, idx2, g1, g2, st); break;
-    case 5: launch_bwd<5>(p1, p2, b, n, m, gd1, gd2, idx1, idx2, g1, g2, st); break;
-    default: launch_bwd<6>(p1, p2, b, n, m, gd1, gd2, idx1, idx2, g1, g2, st); break;
-  }
+  with_dim(d, [&](auto dc) {
+    launch_bwd<decltype(dc)::value>(p1, p2, b, n, m, gd1, gd2, idx1, idx2, g1, g2, st);
+  });
   return check_launch(what);
 }
 
@@ -267,7 +263,7 @@ using namespace pcfm;
 
 extern "C" int pcfm_chamfer_nd_abi_version(void) { return PCFM_CHAMFER_ND_ABI_VERSION; }
 
-extern "C" int pcfm_chamfer_nd_supported(int d) { return d == 2 || d == 3 || d == 5 || d == 6; }
+extern "C" int pcfm_chamfer_nd_supported(int d) { return point_dim_ok(d); }
 
 extern "C" size_t pcfm_chamfer_nd_workspace_bytes(int b, int n, int m, int d) {
   if (b <= 0 || n < 0 || m < 0 || !pcfm_chamfer_nd_supported(d) || !sizes_fit(b, n, m)) return 0;

@@ -12,7 +12,7 @@
 //     (csrc/Makefile NOPK).
 #pragma once
 
-#include "pcfm_common.hpp"
+#include "points.hpp"
 
 namespace pcfm {
 
@@ -23,33 +23,6 @@ constexpr int kPerBlock = kQ * kThreads;
 // candidates per wave-uniform group load: a group and the prefetched next one
 // are 2 * group_of(D) * D SGPRs, 48 at most
 constexpr int group_of(int d) { return d <= 3 ? 8 : 4; }
-
-// c, q: D components each, float or double (the EMD's double entries).  ONE
-// fixed chain (the build has -ffp-contract=off):
-//   acc = d1*d1; acc = fma(d0, d0, acc); acc = fma(dk, dk, acc) for k = 2..D-1,
-//   dk = c[k] - q[k]
-// (c - q)^2 and (q - c)^2 have the same bits, so the direction does not matter.
-// At D = 3 that is sqdist3 (pcfm_common.hpp), the oracle's chain, in both types;
-// fmaT is its fused multiply-add by type.
-template <int D, typename T>
-__device__ __forceinline__ T sqdist_nd(const T* c, const T* q) {
-  const T d1 = c[1] - q[1];
-  T acc = d1 * d1;
-  const T d0 = c[0] - q[0];
-  acc = fmaT<T>(d0, d0, acc);
-#pragma unroll
-  for (int k = 2; k < D; ++k) {
-    const T dk = c[k] - q[k];
-    acc = fmaT<T>(dk, dk, acc);
-  }
-  return acc;
-}
-
-// Split merge key: d >= 0, so a 64-bit atomicMin on it orders by "smaller
-// distance, then lower index" and does not depend on arrival order.
-__device__ __forceinline__ unsigned long long pack_key(float d, int idx) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)idx;
-}
 
 // This lane's kQ queries: points qbase + q * kThreads + threadIdx.x of `cloud`
 // (nq points).  A ragged tail reads the last point; the caller does not store it.

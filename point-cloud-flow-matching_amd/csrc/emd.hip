@@ -534,17 +534,6 @@ int matchcost_bwd(const T* gcost, const T* xyz1, const T* xyz2, const T* match, 
                       });
 }
 
-// f(integral_constant<int, d>) for a d that emd_entry has accepted
-template <class F>
-void with_dim(int d, F&& f) {
-  switch (d) {
-    case 2: f(std::integral_constant<int, 2>{}); break;
-    case 3: f(std::integral_constant<int, 3>{}); break;
-    case 5: f(std::integral_constant<int, 5>{}); break;
-    default: f(std::integral_constant<int, 6>{}); break;
-  }
-}
-
 }  // namespace
 }  // namespace pcfm
 
@@ -604,10 +593,10 @@ extern "C" int pcfm_emd_matchcost_bwd_f64(const double* grad_cost, const double*
 // The pcfm_emd_nd.h entries: D = 2, 3, 5, 6 components, float.
 extern "C" int pcfm_emd_nd_abi_version(void) { return PCFM_EMD_ND_ABI_VERSION; }
 
-extern "C" int pcfm_emd_nd_supported(int d) { return emd_dim_ok(d) ? 1 : 0; }
+extern "C" int pcfm_emd_nd_supported(int d) { return point_dim_ok(d) ? 1 : 0; }
 
 extern "C" size_t pcfm_emd_nd_workspace_bytes(int b, int n, int m, int d) {
-  if (b < 0 || n < 0 || m < 0 || !emd_dim_ok(d)) return 0;
+  if (b < 0 || n < 0 || m < 0 || !point_dim_ok(d)) return 0;
   return EmdPlan(b, n, m, d, sizeof(float)).bytes;
 }
 

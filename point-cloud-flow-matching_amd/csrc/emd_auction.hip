@@ -21,7 +21,7 @@
 //          turned); the wave's best is one unsigned max of the key
 //          (~float bits of w) << 32 | ~j -- w >= +0, so the bits order like the
 //          values, and the max is the lowest w and, among equals, the lowest j --
-//          through the cross-lane max-scan of fps.hip; the second best is a second
+//          through wave_umax, the cross-lane max-scan; the second best is a second
 //          max over "my second best where I hold the winner, my best elsewhere".
 //          Lane 0 forms the bid and sends (bid bits) << 32 | ~i to slot[j1] with one
 //          64-bit LDS max: the highest bid, the lowest person among equals,
@@ -46,8 +46,7 @@
 // Nothing here trusts a float for an address: every index into LDS is a person or
 // an object the code itself numbered, so non-finite coordinates change what is
 // matched, never where anything is read or written.
-#include "chamfer_search.hpp"
-#include "pcfm_common.hpp"
+#include "points.hpp"
 
 #include <cmath>
 
@@ -60,43 +59,9 @@ constexpr int kAucThreads = 1024;   // 4 waves per SIMD: at most 128 VGPRs per l
 constexpr int kAucWaves = kAucThreads / 64;
 constexpr int kAucMaxPoints = 2048;
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
-
 constexpr size_t auc_lds_bytes(int n, int d) { return (size_t)n * (8 * d + 24); }
 static_assert(auc_lds_bytes(kAucMaxPoints, 6) <= (size_t)kLdsBytesMax - 1024,
               "the auction's state must fit the dynamic LDS cap");
-
-// One step of the max-scan by data-parallel-primitive moves; a lane without a
-// source reads 0, below every key in use.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ u32 auc_dpp_max(u32 v) {
-  const u32 o = __builtin_amdgcn_update_dpp(0u, v, CTRL, ROWS, 0xf, false);
-  return o > v ? o : v;
-}
-template <int CTRL, int ROWS>
-__device__ __forceinline__ u64 auc_dpp_max(u64 v) {
-  const u32 lo = __builtin_amdgcn_update_dpp(0u, (u32)v, CTRL, ROWS, 0xf, false);
-  const u32 hi = __builtin_amdgcn_update_dpp(0u, (u32)(v >> 32), CTRL, ROWS, 0xf, false);
-  const u64 o = ((u64)hi << 32) | lo;
-  return o > v ? o : v;
-}
-__device__ __forceinline__ u32 auc_lane63(u32 v) { return __builtin_amdgcn_readlane(v, 63); }
-__device__ __forceinline__ u64 auc_lane63(u64 v) {
-  return ((u64)auc_lane63((u32)(v >> 32)) << 32) | auc_lane63((u32)v);
-}
-
-// The wave's largest value, in every lane (the scan of fps.hip's fps_wave_max).
-template <class T>
-__device__ __forceinline__ T auc_wave_max(T v) {
-  v = auc_dpp_max<0x111, 0xf>(v);   // row_shr:1
-  v = auc_dpp_max<0x112, 0xf>(v);   // row_shr:2
-  v = auc_dpp_max<0x114, 0xf>(v);   // row_shr:4
-  v = auc_dpp_max<0x118, 0xf>(v);   // row_shr:8: lane 15 of a row holds the row's
-  v = auc_dpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-  v = auc_dpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds all
-  return auc_lane63(v);
-}
 
 // Point i of a cloud kept one row per component.
 template <int D>
@@ -135,19 +100,19 @@ __device__ __forceinline__ void auc_bid(const AucLds& s, int n, int i, float eps
     b1 = best ? w : b1;
     j1 = best ? j : j1;
   }
-  const u64 key = lane < n ? ((u64)(~__float_as_uint(b1)) << 32) | (u32)~(u32)j1 : 0;
-  const u64 kmax = auc_wave_max(key);
-  u32 jb = ~(u32)kmax;
+  const u64 key = lane < n ? max_key(~__float_as_uint(b1), j1) : 0;
+  const u64 kmax = wave_umax(key);
+  u32 jb = (u32)max_key_index(kmax);
   jb = jb < (u32)n ? jb : (u32)(n - 1);
-  const float w1 = __uint_as_float(~(u32)(kmax >> 32));
+  const float w1 = __uint_as_float(~key_hi(kmax));
   const float other = key == kmax ? b2 : b1;   // a lane without an object holds +inf
-  float w2 = __uint_as_float(~auc_wave_max((u32)~__float_as_uint(other)));
+  float w2 = __uint_as_float(~wave_umax((u32)~__float_as_uint(other)));
   if (n == 1) w2 = w1;
   if (lane == 0) {
     const float pj = s.price[jb];
     float bid = pj + ((w2 - w1) + eps);   // v1 - v2 = w2 - w1
     if (!(bid > pj)) bid = __uint_as_float(__float_as_uint(pj) + 1u);
-    atomicMax(&s.slot[jb], ((u64)__float_as_uint(bid) << 32) | (u32)~(u32)i);
+    atomicMax(&s.slot[jb], max_key(__float_as_uint(bid), i));
     s.assigned[i] = -2 - (int)jb;
   }
 }
@@ -209,7 +174,7 @@ __global__ void __launch_bounds__(kAucThreads)
       m = c1 > m ? c1 : m;
     }
   }
-  const u32 mw = auc_wave_max(__float_as_uint(m));   // m >= +0: the bits order like the values
+  const u32 mw = wave_umax(__float_as_uint(m));   // m >= +0: the bits order like the values
   if (lane == 0) redf[wave] = __uint_as_float(mw);
   __syncthreads();
   float cmax = redf[0];
@@ -255,11 +220,11 @@ __global__ void __launch_bounds__(kAucThreads)
       int* next = &cnt[cur ^ 1];
       for (int j = t; j < n; j += kAucThreads) {
         const u64 sl = s.slot[j];
-        const u32 hb = (u32)(sl >> 32);
+        const u32 hb = key_hi(sl);
         if (hb != __float_as_uint(s.price[j])) {
           s.price[j] = __uint_as_float(hb);
           const int prev = s.owner[j];
-          s.owner[j] = (int)~(u32)sl;
+          s.owner[j] = max_key_index(sl);
           if (prev >= 0) {
             s.assigned[prev] = -1;
             const int p = atomicAdd(next, 1);
@@ -271,7 +236,7 @@ __global__ void __launch_bounds__(kAucThreads)
         const int av = s.assigned[i];
         if (av <= -2) {
           const int j = -2 - av;
-          if ((int)~(u32)s.slot[j] == i) {
+          if (max_key_index(s.slot[j]) == i) {
             s.assigned[i] = j;
           } else {
             s.assigned[i] = -1;
@@ -309,8 +274,7 @@ __global__ void __launch_bounds__(kAucThreads)
       sum += (double)sqdist_nd<D>(y, x);
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
+  wave_add(sum);
   if (lane == 0) redd[wave] = sum;
   __syncthreads();
   if (t == 0) {
@@ -340,7 +304,7 @@ using namespace pcfm;
 extern "C" int pcfm_emd_auction_abi_version(void) { return PCFM_EMD_AUCTION_ABI_VERSION; }
 
 extern "C" int pcfm_emd_auction_max_points(int d) {
-  return d == 2 || d == 3 || d == 5 || d == 6 ? kAucMaxPoints : 0;
+  return point_dim_ok(d) ? kAucMaxPoints : 0;
 }
 
 extern "C" size_t pcfm_emd_auction_workspace_bytes(int b, int n, int d) {
@@ -368,10 +332,10 @@ extern "C" int pcfm_emd_auction_f32(const float* p1, const float* p2, int b, int
                  pcfm_emd_auction_workspace_bytes(b, n, d));
   if (b == 0) return PCFM_OK;
   const hipStream_t st = (hipStream_t)stream;
-  switch (d) {
-    case 2: return launch_auction<2>(p1, p2, b, n, eps_rel, max_rounds, assignment, cost, rounds, st);
-    case 3: return launch_auction<3>(p1, p2, b, n, eps_rel, max_rounds, assignment, cost, rounds, st);
-    case 5: return launch_auction<5>(p1, p2, b, n, eps_rel, max_rounds, assignment, cost, rounds, st);
-    default: return launch_auction<6>(p1, p2, b, n, eps_rel, max_rounds, assignment, cost, rounds, st);
-  }
+  int rc = PCFM_OK;
+  with_dim(d, [&](auto dc) {
+    rc = launch_auction<decltype(dc)::value>(p1, p2, b, n, eps_rel, max_rounds, assignment, cost,
+                                             rounds, st);
+  });
+  return rc;
 }

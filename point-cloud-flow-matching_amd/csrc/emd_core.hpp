@@ -6,7 +6,7 @@
 // components, float) are written over it.
 #pragma once
 
-#include "pcfm_common.hpp"
+#include "points.hpp"
 
 #include <algorithm>
 #include <cstdlib>
@@ -69,6 +69,8 @@ __device__ __forceinline__ T sum_parts(const T* part, int S, size_t stride, size
 
 template <typename T>
 __device__ __forceinline__ T block_sum(T v, T* red) {
+  // wave_add written out: through the call the f32 kernels' slot store is
+  // scheduled differently ("What the point-cloud kernels share")
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -90,16 +92,13 @@ __device__ __forceinline__ void emd_cost_fin(const T* __restrict__ part, int per
   const int bb = blockIdx.x, lane = threadIdx.x;
   T t = 0;
   for (int i = lane; i < per_b; i += 64) t += part[(size_t)bb * per_b + i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  wave_add(t);
   if (lane == 0) cost[bb] = t;
 }
 
 // ---------------------------------------------------------------------------
 // Host side: one plan of the workspace, one prologue, one launch sequence.
 // ---------------------------------------------------------------------------
-constexpr bool emd_dim_ok(int d) { return d == 2 || d == 3 || d == 5 || d == 6; }
-
 // Elements of a pack: a point's d coordinates and the coefficient it carries
 // into a pass, in whole 16-byte (float) slots -- one for d <= 3, two above.
 constexpr int emd_pack_elems(int d) { return d <= 3 ? 4 : 8; }
@@ -181,7 +180,7 @@ template <typename T, typename Launch>
 int emd_entry(const char* who, int b, int n, int m, int d, void* ws, size_t ws_bytes,
               hipStream_t st, std::initializer_list<EmdOut<T>> outs, Launch&& launch) {
   PCFM_CHECK_ARG(b >= 0 && n >= 0 && m >= 0, "%s: negative size", who);
-  PCFM_CHECK_ARG(emd_dim_ok(d), "%s: unsupported dimension %d", who, d);
+  PCFM_CHECK_ARG(point_dim_ok(d), "%s: unsupported dimension %d", who, d);
   const EmdPlan p(b, n, m, d, sizeof(T));
   PCFM_CHECK_ARG(ws_bytes >= p.bytes, "%s: workspace %zu < %zu bytes", who, ws_bytes, p.bytes);
   if (b == 0) return PCFM_OK;

@@ -30,7 +30,7 @@
 // (~index >= 2^31), and never stores to a slot; a wave without a point leaves
 // its slot at the 0 the kernel starts with.  The index a round yields is always
 // the index of a point some lane owns, whatever the coordinates hold.
-#include "pcfm_common.hpp"
+#include "points.hpp"
 
 #include "../../include/pcfm_fps.h"
 
@@ -41,8 +41,6 @@ constexpr int kFpsThreads = 512;    // 2 waves per SIMD: at most 256 VGPRs per l
 constexpr int kFpsWaves = kFpsThreads / 64;
 constexpr int kFpsMaxP = 40;        // points per thread, at most: 4 * 40 registers of state
 constexpr int kResident = kFpsThreads * kFpsMaxP;
-
-typedef unsigned long long u64;
 
 struct FpsSlots {
   u64 key[2][kFpsWaves];
@@ -64,34 +62,12 @@ __device__ __forceinline__ void fps_init_slots(FpsSlots& sm) {
   __syncthreads();
 }
 
-// The wave's largest key, in every lane: a max-scan by data-parallel-primitive
-// moves (a lane without a source reads 0, below every key) leaves it in lane 63.
-template <int CTRL, int ROWS>
-__device__ __forceinline__ u64 fps_dpp_max(u64 v) {
-  const unsigned lo = __builtin_amdgcn_update_dpp(0u, (unsigned)v, CTRL, ROWS, 0xf, false);
-  const unsigned hi = __builtin_amdgcn_update_dpp(0u, (unsigned)(v >> 32), CTRL, ROWS, 0xf, false);
-  const u64 o = ((u64)hi << 32) | lo;
-  return o > v ? o : v;
-}
-
-__device__ __forceinline__ u64 fps_wave_max(u64 v) {
-  v = fps_dpp_max<0x111, 0xf>(v);   // row_shr:1
-  v = fps_dpp_max<0x112, 0xf>(v);   // row_shr:2
-  v = fps_dpp_max<0x114, 0xf>(v);   // row_shr:4
-  v = fps_dpp_max<0x118, 0xf>(v);   // row_shr:8: lane 15 of a row holds the row's
-  v = fps_dpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-  v = fps_dpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds all
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)v, 63);
-  const unsigned hi = __builtin_amdgcn_readlane((unsigned)(v >> 32), 63);
-  return ((u64)hi << 32) | lo;
-}
-
 // The block's farthest point of round j: `key` / `c` are the thread's (key 0:
 // the thread owns no point).  Returns the index, the coordinates in `sel`.
 template <int K>
 __device__ __forceinline__ int fps_block_argmax(FpsSlots& sm, int j, u64 key, const float (&c)[K],
                                                 float (&sel)[K]) {
-  const u64 wmax = fps_wave_max(key);
+  const u64 wmax = wave_umax(key);
   const int buf = j & 1;
   if (key != 0 && key == wmax) {    // one lane of a wave that owns a point
     const int wave = threadIdx.x >> 6;
@@ -113,11 +89,7 @@ __device__ __forceinline__ int fps_block_argmax(FpsSlots& sm, int j, u64 key, co
   sel[0] = v.x;
   sel[1] = v.y;
   if constexpr (K == 3) sel[2] = v.z;
-  return (int)~(unsigned)best;
-}
-
-__device__ __forceinline__ u64 fps_key(float v, int i) {
-  return ((u64)__float_as_uint(v) << 32) | (u64)(~(unsigned)i);
+  return max_key_index(best);
 }
 
 // idx[0] and the coordinates of the first pick
@@ -181,7 +153,7 @@ __global__ void __launch_bounds__(kFpsThreads)
 #pragma unroll
       for (int k = 0; k < K; ++k) bc[k] = far ? x[p][k] : bc[k];
     }
-    const u64 key = t < n ? fps_key(bv, t + bp * T) : 0;
+    const u64 key = t < n ? max_key(__float_as_uint(bv), t + bp * T) : 0;
     const int win = fps_block_argmax<K>(sm, j, key, bc, sel);
     if (t == 0) ip[j] = win;
   }
@@ -222,7 +194,7 @@ __global__ void __launch_bounds__(kFpsThreads)
         for (int k = 0; k < K; ++k) bc[k] = p[k];
       }
     }
-    const u64 key = t < n ? fps_key(bv, bi) : 0;
+    const u64 key = t < n ? max_key(__float_as_uint(bv), bi) : 0;
     const int win = fps_block_argmax<K>(sm, j, key, bc, sel);
     if (t == 0) ip[j] = win;
   }
@@ -276,7 +248,7 @@ using namespace pcfm;
 
 extern "C" int pcfm_fps_abi_version(void) { return PCFM_FPS_ABI_VERSION; }
 
-extern "C" int pcfm_fps_supported(int d) { return d == 2 || d == 3 || d == 5 || d == 6; }
+extern "C" int pcfm_fps_supported(int d) { return point_dim_ok(d); }
 
 extern "C" int pcfm_fps_resident_points(void) { return kResident; }
 

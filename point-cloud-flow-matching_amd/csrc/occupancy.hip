@@ -36,7 +36,7 @@
 // at a stride of d floats.  A wave's 64 rows are contiguous, so every fetched
 // line is used in full at d = 3 and to one half at d = 6, where the colour
 // shares the line.
-#include "pcfm_common.hpp"
+#include "points.hpp"
 
 #include "../../include/pcfm_occupancy.h"
 
@@ -225,7 +225,7 @@ using namespace pcfm;
 extern "C" int pcfm_occupancy_abi_version(void) { return PCFM_OCCUPANCY_ABI_VERSION; }
 
 extern "C" int pcfm_occupancy_supported(int d, int r) {
-  return (d == 3 || d == 5 || d == 6) && r >= 3 && r <= 32;
+  return point_dim_ok(d) && d >= 3 && r >= 3 && r <= 32;   // the cells are over xyz
 }
 
 extern "C" size_t pcfm_occupancy_workspace_bytes(int s, int n, int d, int r) {

@@ -21,8 +21,7 @@ constexpr int kAdamwChunk = PCFM_ADAMW_CHUNK;
 constexpr int kVec4 = 1, kSkip = 2, kEma = 4;
 
 __device__ __forceinline__ double block_sum_d(double a, double* sh) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
+  wave_add(a);
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   if (lane == 0) sh[w] = a;
   __syncthreads();

@@ -79,11 +79,19 @@ __device__ __forceinline__ double fmaT<double>(double a, double b, double c) {
   return __builtin_fma(a, b, c);
 }
 
-// Wave-wide (64 lanes) butterfly reductions.  wave_sum leaves the sum in every
-// lane; wave_max / wave_min return it wave-uniform (one scalar register).
-__device__ __forceinline__ float wave_sum(float x) {
+// Wave-wide (64 lanes) butterfly reductions.  wave_add (float, double, int)
+// turns an accumulator into the wave's sum in every lane, added in ONE order --
+// xor offsets 32 down to 1 -- which is part of every deterministic sum built on
+// it; wave_sum is the same as an expression.  wave_max / wave_min return their
+// result wave-uniform (one scalar register).
+template <typename T>
+__device__ __forceinline__ void wave_add(T& x) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+}
+template <typename T>
+__device__ __forceinline__ T wave_sum(T x) {
+  wave_add(x);
   return x;
 }
 __device__ __forceinline__ float wave_max(float v) {
@@ -96,6 +104,40 @@ __device__ __forceinline__ float wave_min(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
+typedef unsigned int u32;
+typedef unsigned long long u64;   // what the 64-bit atomics take
+
+// The wave's largest unsigned value, in every lane: a max-scan by
+// data-parallel-primitive moves (a lane without a source reads 0, below every
+// key in use) leaves it in lane 63, which is read back wave-uniform.  No LDS
+// traffic.  With the ordering keys of points.hpp this is a wave argmax / argmin.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ u32 dpp_umax(u32 v) {
+  const u32 o = __builtin_amdgcn_update_dpp(0u, v, CTRL, ROWS, 0xf, false);
+  return o > v ? o : v;
+}
+template <int CTRL, int ROWS>
+__device__ __forceinline__ u64 dpp_umax(u64 v) {
+  const u32 lo = __builtin_amdgcn_update_dpp(0u, (u32)v, CTRL, ROWS, 0xf, false);
+  const u32 hi = __builtin_amdgcn_update_dpp(0u, (u32)(v >> 32), CTRL, ROWS, 0xf, false);
+  const u64 o = ((u64)hi << 32) | lo;
+  return o > v ? o : v;
+}
+__device__ __forceinline__ u32 lane63(u32 v) { return __builtin_amdgcn_readlane(v, 63); }
+__device__ __forceinline__ u64 lane63(u64 v) {
+  return ((u64)lane63((u32)(v >> 32)) << 32) | lane63((u32)v);
+}
+template <class T>
+__device__ __forceinline__ T wave_umax(T v) {
+  v = dpp_umax<0x111, 0xf>(v);   // row_shr:1
+  v = dpp_umax<0x112, 0xf>(v);   // row_shr:2
+  v = dpp_umax<0x114, 0xf>(v);   // row_shr:4
+  v = dpp_umax<0x118, 0xf>(v);   // row_shr:8: lane 15 of a row holds the row's
+  v = dpp_umax<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+  v = dpp_umax<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds all
+  return lane63(v);
+}
+
 // lane l's value of v, wave-uniform (v_readlane; l uniform)
 __device__ __forceinline__ float rlf(float v, int l) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));

@@ -572,6 +572,10 @@ backend = types.SimpleNamespace(
 )
 
 
+# the point widths of the N-D entries (csrc/points.hpp: point_dim_ok)
+POINT_DIMS = (2, 3, 5, 6)
+
+
 # --------------------------------------------------------------------------
 # chamfer_3D (chamfer_cuda.cpp:17-32) and chamfer_2D / chamfer_5D / chamfer_6D
 # (ChamferDistancePytorch/chamfer{2,5,6}D/chamfer_cuda.cpp): caller-allocated
@@ -595,7 +599,7 @@ def _chamfer_nd_shapes(xyz1, xyz2, d, per_point, per_coord):
     for t, nm, k in per_coord:
         if tuple(t.shape) != (b, (n, m)[k], d):
             raise RuntimeError(f"{nm} has shape {tuple(t.shape)}, expected {(b, (n, m)[k], d)}")
-    if d not in (2, 3, 5, 6):
+    if d not in POINT_DIMS:
         raise RuntimeError(f"unsupported point dimension {d}")
     return b, n, m, d
 
@@ -682,7 +686,7 @@ def chamfer_cross_forward(a: torch.Tensor, b: torch.Tensor):
         raise RuntimeError(f"expected (S, N, D) and (R, M, D), got {tuple(a.shape)} and "
                            f"{tuple(b.shape)}")
     (s, n, d), (r, m) = a.shape, b.shape[:2]
-    if d not in (2, 3, 5, 6):
+    if d not in POINT_DIMS:
         raise RuntimeError(f"unsupported point dimension {d}")
     if host:
         return cpu_ops.chamfer_cross_forward(a, b)
@@ -710,7 +714,7 @@ def farthest_point_sample(points: torch.Tensor, m: int, start=None, gather: bool
     if points.dim() != 3:
         raise RuntimeError(f"expected points (B, N, D), got {tuple(points.shape)}")
     b, n, d = points.shape
-    if d not in (2, 3, 5, 6):
+    if d not in POINT_DIMS:
         raise RuntimeError(f"unsupported point dimension {d}")
     m = int(m)
     if m < 0:
@@ -860,7 +864,7 @@ emd_cuda = types.SimpleNamespace(approxmatch_forward=approxmatch_forward,
 # the same over D-component points, D in {2, 3, 5, 6}, float32
 # (include/pcfm_emd_nd.h, csrc/emd.hip); every component has the same weight
 # --------------------------------------------------------------------------
-EMD_ND_DIMS = (2, 3, 5, 6)
+EMD_ND_DIMS = POINT_DIMS
 
 
 def _emd_nd_check(p1, p2, match=None, grad_cost=None):

@@ -237,7 +237,7 @@ def test_einval_writes_nothing(ops):
     pts = torch.randn(b, n, d, device=DEV)
     idx = torch.full((b, m), -7, dtype=torch.int32, device=DEV)
     out = torch.full((b, m, d), 3.5, device=DEV)
-    with pytest.raises(_lib.PcfmError, match="status -1"):
+    with pytest.raises(_lib.PcfmError, match=r"status -1\): fps: unsupported dimension 4$"):
         _lib.call("pcfm_fps", pts.data_ptr(), b, n, d, m, None, idx.data_ptr(), out.data_ptr(),
                   None, 0, torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()

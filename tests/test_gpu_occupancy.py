@@ -201,7 +201,9 @@ def test_einval_writes_nothing(ops):
                            (3, 33, ws.numel()), (3, 28, 28 ** 3 * 4 - 1), (6, 9, 0)):
         pts = torch.randn(s, n, d, device=DEV)
         counts = torch.full((max(r, 3) ** 3,), -7, dtype=torch.int32, device=DEV)
-        with pytest.raises(_lib.PcfmError, match="status -1"):
+        text = (r"occupancy: workspace \d+ < \d+ bytes$" if ws_bytes < ws.numel() else
+                f"occupancy: unsupported dimension {d} or resolution {r}$")
+        with pytest.raises(_lib.PcfmError, match=r"status -1\): " + text):
             _lib.call("pcfm_occupancy_counts", pts.data_ptr(), s, n, d, r, counts.data_ptr(),
                       ws.data_ptr(), ws_bytes, st)
         torch.cuda.synchronize()
